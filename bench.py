@@ -16,7 +16,13 @@ Multi-GPU: `--gpus N` starts N ranks itself (torch.distributed.run, one process 
 before anything touches the GPU, or joins the N ranks a launcher already started; the ranks meet in
 one bucketed in-place all-reduce of the flat gradient buffer per step (parallel.BucketedAllReduce).
 
-Also reported on the same JSON line:
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets the --config workload up, runs W warm-up and K timed
+steps, writes the last timed step's outputs if --dump-outputs DIR is given, and prints the result line (metric,
+value, unit, higher_is_better, dtype, ms_per_step, the configuration and the arithmetic step roofline).  Everything
+else is measured only with --full: the per-kernel HIP events and the dominant kernel's roofline, the other GEMM mode,
+the further workloads (--also), the fold-0 AUC and the CPU baseline.
+
+With --full, also reported on the same JSON line:
   roofline      the dominant kernel's achieved HBM rate (algorithmic bytes per launch / its
                 HIP-event duration inside the timed steps, events on the launch stream) vs 8 TB/s;
   cpu_baseline  the reference formulation (oracle/ref_model.py: torch-CPU fp32, per-edge GEMMs,
@@ -405,6 +411,31 @@ def step_roofline(N, R, D, T, M, gemm, features, ms_per_step, edge_mfma="hilo", 
                                "note": "SURVEY §8(d) as written; not a lower bound of this formulation"}}
 
 
+DUMP_ROWS = 16384      # --dump-outputs: rows of E and of its gradient that are kept when the table has more
+
+
+def dump_outputs(path, loss, P, G):
+    """--dump-outputs: what the last timed training step handed its caller, as float32 <name>.npy files under
+    ``path``: the loss sum it returned (loss), the parameters it updated (param_<name>) and the gradients it left in
+    the caller's buffer (grad_<name>).  Of E and its gradient a fixed seeded sample of DUMP_ROWS rows is kept when the
+    table has more (their indices: E_rows, float64), which bounds the files at about 40 MB at any workload size."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    N = P["E"].shape[0]
+    rows = None
+    if N > DUMP_ROWS:
+        idx = np.sort(np.random.default_rng(0).choice(N, DUMP_ROWS, replace=False))
+        np.save(os.path.join(path, "E_rows.npy"), idx.astype(np.float64))
+        rows = torch.as_tensor(idx, device=P["E"].device)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().cpu().numpy().reshape(1))
+    for prefix, buf in (("param", P), ("grad", G)):
+        for name, v in buf.views.items():
+            if name == "E" and rows is not None:
+                v = v[rows]
+            np.save(os.path.join(path, f"{prefix}_{name}.npy"), v.detach().float().cpu().numpy())
+
+
 def rank_consistency(buf):
     """After the timed steps: the largest |params - rank 0's params| over all ranks (0.0 when every rank holds
     bitwise the same parameters, as the replicated Adam on all-reduced gradients must).  ``buf``: the rank's flat
@@ -421,8 +452,9 @@ def rank_consistency(buf):
 
 
 def run_workload(cid, args, world, rank, dev, gemm, other_mode, probe_kernels=True, shard=None, steps=None,
-                 warmup=None):
-    """Build one workload on the GPU, time W + K training steps, return the bench-line fields."""
+                 warmup=None, dump_dir=None):
+    """Build one workload on the GPU, time W + K training steps, return the bench-line fields.  ``dump_dir``: rank 0
+    writes the last timed step's outputs there (dump_outputs)."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -483,7 +515,7 @@ def run_workload(cid, args, world, rank, dev, gemm, other_mode, probe_kernels=Tr
     elif shard == "spmm" and world > 1:
         eng.spmm_shard = RelationShard(R, N)     # row-partitioned SpMMs, node GEMMs replicated
 
-    def timed_run(mode, probe, edge_mfma=emfma):
+    def timed_run(mode, probe, edge_mfma=emfma, dump=False):
         """W warm-up steps, then K timed steps between barriers + synchronize; max over ranks."""
         eng.gemm = mode
         eng.edge_mfma = edge_mfma
@@ -510,9 +542,11 @@ def run_workload(cid, args, world, rank, dev, gemm, other_mode, probe_kernels=Tr
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
         probe_out, eng.probe = eng.probe, None
+        if dump and rank == 0:
+            dump_outputs(dump_dir, loss, P, G)
         return elapsed, float(loss.item()) / T, probe_out
 
-    elapsed, loss_val, probe = timed_run(gemm, probe_kernels)
+    elapsed, loss_val, probe = timed_run(gemm, probe_kernels, dump=dump_dir is not None)
     consist = rank_consistency(P.buf) if world > 1 else None
     out = {"value": M / (elapsed / steps), "ms_per_step": elapsed / steps * 1e3,
            "scaling": cfg["scaling"], "dtype": DTYPE_BF16[emfma] if feat == "bf16" else DTYPE[gemm],
@@ -583,6 +617,13 @@ def main():
                          "'Ne' = edge-partitioned, 'Nr' = with relation-sharded node tables, 'Ns' = with "
                          "row-partitioned SpMMs; default 4 5 (BASELINE configs 4 and 5), plus 4e with more than one "
                          "GPU; none to skip")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel HIP events and the dominant "
+                         "kernel's roofline, the other GEMM mode, the --also workloads, the fold-0 AUC and the CPU "
+                         "baseline (each with its own --no-... / --also none switch); without --full none of them runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, updated parameters, "
+                         "gradients; a fixed seeded sample of E's rows) as float32 DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-fold0-auc", action="store_true",
                     help="skip the metric's second part: the fold-0 eval AUC (bundled weights, and trained from scratch)")
@@ -608,6 +649,11 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, dump, print
+        args.also, args.no_other_mode, args.no_fold0_auc, args.no_cpu_baseline = ["none"], True, True, True
     if args.shard is None:
         # node-row partitioning beats edge partitioning at every config once there is more than one rank: the node
         # work is divided instead of replicated (measured per-rank compute, collective volumes)
@@ -634,7 +680,8 @@ def main():
             dist.init_process_group(backend)
     dev = torch.device("cuda", local)
 
-    main_out = run_workload(args.config, args, world, rank, dev, args.gemm, not args.no_other_mode)
+    main_out = run_workload(args.config, args, world, rank, dev, args.gemm, not args.no_other_mode,
+                            probe_kernels=args.full, dump_dir=args.dump_outputs)
     main_out.pop("steps"), main_out.pop("warmup")
     result = {
         "metric": "adjacency edges/s per IDDGCN training step (pos fwd + neg fwd + bwd + Adam)",

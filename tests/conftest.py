@@ -8,7 +8,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REFERENCE = "/root/reference/datasets/prediction_datasets"
+# the reference's bundled data files that the fold construction and the h5 reader are pinned against (copies)
+REFERENCE = os.path.join(GOLDEN, "prediction_datasets")
 
 
 def pytest_configure(config):

@@ -2,8 +2,6 @@
 utils1.py:741-867 (pandas merges, sklearn KFold) in all four modes, and — mode 0 — against the
 reference's bundled fold files (tests/golden/fold{k}_data.npz, themselves reproduced bit-for-bit by
 the oracle, tests/test_oracle.py)."""
-import os
-
 import numpy as np
 import pandas as pd
 import pytest
@@ -54,7 +52,6 @@ def test_splits_match_oracle_all_modes(mode):
         assert np.array_equal(b.to_numpy(), d.to_numpy())
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference datasets not present")
 @pytest.mark.parametrize("k", range(5))
 def test_make_fold_reproduces_bundled_files(k, golden):
     f = golden(f"fold{k}_data.npz")
@@ -64,7 +61,6 @@ def test_make_fold_reproduces_bundled_files(k, golden):
     assert np.array_equal(ours["X_train_neg"][0].astype(np.int64), f["X_train_neg"].astype(np.int64))
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference datasets not present")
 @pytest.mark.parametrize("mode", [1, 2, 3])
 def test_make_fold_cold_start_modes_follow_the_script(mode):
     """Modes 1-3 (IDDGCN.py:312-363 with mode != 0): the product's make_fold equals the oracle's restatement

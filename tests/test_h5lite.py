@@ -1,6 +1,6 @@
 """Keras-h5 weight IO without h5py (iddgcn_amd/h5lite.py).
 
-* reader: the reference's five bundled weight files (read where /root/reference exists) equal the
+* reader: the reference's five bundled weight files (copies under tests/golden/prediction_datasets) equal the
   committed npz fixtures, which were converted with h5py (oracle/convert_h5.py);
 * writer: save_weights(.h5) round-trips through the reader; when the image's secondary interpreter
   with h5py is present, h5py reads the written file back identically (the file is real HDF5).
@@ -14,12 +14,12 @@ import pytest
 
 from iddgcn_amd import get_IDDGCN_Model, h5lite
 from iddgcn_amd.weights_io import NAMES, load_h5
+from tests.conftest import REFERENCE
 
-REF_W = "/root/reference/datasets/prediction_datasets/weights/IDDGCN_normal"
+REF_W = os.path.join(REFERENCE, "weights", "IDDGCN_normal")
 H5PY_PY = "/opt/conda/bin/python3.9"
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_W), reason="reference weight files only in the build container")
 @pytest.mark.parametrize("k", range(5))
 def test_reader_matches_h5py_conversion(k, golden):
     w = load_h5(os.path.join(REF_W, f"mode0_fold{k}_epoch5000_learnRate0.001_batchsize100_embdim64_weight.h5"))
@@ -28,7 +28,6 @@ def test_reader_matches_h5py_conversion(k, golden):
         assert np.array_equal(w[n], g[n]), n
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_W), reason="reference weight files only in the build container")
 def test_reader_structure_and_attributes():
     f = h5lite.open_file(os.path.join(REF_W, "mode0_fold0_epoch5000_learnRate0.001_batchsize100_embdim64_weight.h5"))
     assert f.attrs["keras_version"] == "2.7.0" and f.attrs["backend"] == "tensorflow"

@@ -1,6 +1,4 @@
 """The CPU oracle against the reference's own bundled files (pinning)."""
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -12,7 +10,6 @@ from tests.conftest import REFERENCE
 N_ENT, N_REL = 845, 4
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference tree only in the build container")
 @pytest.mark.parametrize("k", range(5))
 def test_split_restatement_reproduces_bundled_folds(k, golden):
     """IDDGCN.py:312-373 + utils1.py:741-867 restated -> the bundled fold files, bit for bit."""
@@ -89,14 +86,13 @@ def test_synth_fixture_grads_torch_consistency(golden):
 
 def test_similarity_oracle_reproduces_reference_outputs(golden):
     """oracle/ref_similarity.py against the reference's own mu_similar0.97.csv / drug_similar0.78.csv
-    (as committed in tests/golden/similarity.npz; re-read from /root/reference when present)."""
+    (as committed in tests/golden/similarity.npz, and as the csv files under tests/golden/prediction_datasets)."""
     import pandas as pd
 
     from oracle.ref_similarity import similar_triples
     g = golden("similarity.npz")
     assert np.array_equal(similar_triples(g["mu_feat"], 0.97, 3, 0), g["mu_triples"])
     assert np.array_equal(similar_triples(g["drug_feat"], 0.78, 2, 661), g["drug_triples"])
-    ref = "/root/reference/datasets/prediction_datasets"
-    if os.path.isdir(ref):
-        assert np.array_equal(pd.read_csv(f"{ref}/mu_similar0.97.csv", header=None).to_numpy(), g["mu_triples"])
-        assert np.array_equal(pd.read_csv(f"{ref}/drug_similar0.78.csv", header=None).to_numpy(), g["drug_triples"])
+    ref = REFERENCE
+    assert np.array_equal(pd.read_csv(f"{ref}/mu_similar0.97.csv", header=None).to_numpy(), g["mu_triples"])
+    assert np.array_equal(pd.read_csv(f"{ref}/drug_similar0.78.csv", header=None).to_numpy(), g["drug_triples"])
