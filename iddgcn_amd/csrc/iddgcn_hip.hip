@@ -2039,6 +2039,15 @@ __device__ __forceinline__ void row_to_planes3(char* row, int lane) {
 //   * epilogue as the v3 kernel: gathered P_r[t] rows (the tile's distinct tails), per-edge coefficients
 //     and sigma' rows (or, accumulating, the old C rows) DMA'd into wave-private slabs ([32][16] fp32, XOR-swizzled 16-B groups); waves 4-7 run
 //     the epilogue of tile t-1 while waves 0-3 run tile t's MFMAs on the same SIMDs; one barrier per tile.
+//   * KS = 2, the gathered-combine forward (NV = R = 1, 2): the k dimension split over wave pairs, 16 waves = four
+//     per SIMD instead of two.  Wave (column group c, k half h) = wave id c + 8h holds the planes of 4 k-steps
+//     (48 VGPRs instead of 96; 120 / 122 VGPRs in all for NV = 1 / 2, no scratch, 138,240 / 154,624 B of LDS),
+//     reads its fragments single-buffered and issues 48 of the tile's 96 MFMAs per column group, in the same
+//     six-product order and hi / lo split.  The k-high wave stages and converts the pair's 4 A rows and hands
+//     hi + lo of k 128..255 over through a 2-KB LDS exchange; the k-low wave owns indices, slabs, coefficients
+//     and the epilogue: act((acc(k 0..127) + acc(k 128..255)) + combine), so a row's result still depends on that
+//     row only.  Two barriers per tile order the single exchange buffer.  Forward at config 3 (T = 4M): 2.94 vs
+//     3.12 ms with two waves per SIMD (DESIGN.md "Kernels").
 __device__ __forceinline__ unsigned lds_u32(const void* p) {
     return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const char*)p;
 }
@@ -2053,18 +2062,24 @@ constexpr int SLAB = TR * CWV;              // floats of a [32 rows][16 columns]
 // epilogue's ds_read_b128 (slot l&15 [+16], group l>>4) is conflict-free in each of its four lane groups
 __device__ __forceinline__ int slab16_off(int slot, int g) { return slot * 16 + 4 * (g ^ ((-(slot >> 2)) & 3)); }
 
-template <int NV, bool AUX, bool BC = false>
-__global__ __launch_bounds__(512) void rowgemm256_b3_kernel(RowGemmP p, int n_ranges) {
+template <int NV, bool AUX, bool BC = false, int KS = 1>
+__global__ __launch_bounds__(512 * KS) void rowgemm256_b3_kernel(RowGemmP p, int n_ranges) {
     using namespace rb3;
     static_assert(NV >= 0 && NV <= 2 && !(NV > 0 && AUX), "b3: gathered forward (NV = R = 1, 2), sigma' backward, plain");
     static_assert(!BC || NV == 0, "BC: one broadcast V row per relation (R <= 2), e.g. dz W_a^T");
+    static_assert(KS == 1 || (KS == 2 && NV > 0), "k-split: the gathered forward only");
     constexpr int NSL = NV + (AUX ? 1 : 0);
     constexpr int WF = NSL * SLAB + 64 + 64 + 32;               // slabs, coef [32][R], idx [64], cmp [32]
-    constexpr int LDSB = 2 * ABYTES + NW * WF * 4;
+    constexpr int KQ = 8 / KS;                                  // k-steps (32 k) of one wave
+    constexpr int XOFF = 2 * ABYTES + NW * WF * 4;              // KS = 2: the pairs' exchange, [2][64 lanes] f32x4 each
+    constexpr int XB = TR * CWV * 4;                            // one pair's partial, 2 KB
+    constexpr int LDSB = XOFF + (KS == 2 ? NW * XB : 0);
     static_assert(LDSB <= 160 * 1024, "LDS budget");
     __shared__ __attribute__((aligned(16))) char lds[LDSB];
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = KS == 2 ? (wid & 7) : wid;                 // column group (and the A rows it stages)
+    const int kh = KS == 2 ? (wid >> 3) : 0;                    // k half
     const int i = lane & 15, g = lane >> 4;
     const int bx = blockIdx.x;
     const int half = (bx >> 3) & 1;
@@ -2084,13 +2099,13 @@ __global__ __launch_bounds__(512) void rowgemm256_b3_kernel(RowGemmP p, int n_ra
     const long long Mlast = (long long)p.M - 1;
     auto clampe = [&](long long e) __attribute__((always_inline)) { return e > Mlast ? Mlast : e; };
 
-    // weight planes: k-step q (32 k), lane l: column c0 + (l&15), k = 32q + 8(l>>4) + e
-    bf16x8 w0[8], w1[8], w2[8];
+    // weight planes: k-step q (32 k), lane l: column c0 + (l&15), k = 32q + 8(l>>4) + e (KS = 2: + 128 kh)
+    bf16x8 w0[KQ], w1[KQ], w2[KQ];
 #pragma unroll
-    for (int q = 0; q < 8; ++q)
+    for (int q = 0; q < KQ; ++q)
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const int k = 32 * q + 8 * g + e;
+            const int k = 32 * q + 8 * g + e + (KS == 2 ? 128 * kh : 0);
             const float wv = p.b_trans ? p.B[(c0 + i) * D + k] : p.B[k * D + c0 + i];
             __bf16 a, b, c;
             split3(wv, a, b, c);
@@ -2238,6 +2253,57 @@ __global__ __launch_bounds__(512) void rowgemm256_b3_kernel(RowGemmP p, int n_ra
     // that k-step's MFMAs): bitwise the same, forward 3.333 vs 3.278 ms, sigma' 3.334 vs 3.274, plain 2.925 vs 2.930
     auto mfma_tile = [&](int bb, f32x4 (&acc)[2]) __attribute__((always_inline)) {
         f32x4 hi0 = {0.f, 0.f, 0.f, 0.f}, lo0 = hi0, hi1 = hi0, lo1 = hi0;
+#define B3_MFMAQ(Q, X0, X1, X2, Y0, Y1, Y2)                                                              \
+        lo0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[Q], X2, lo0, 0, 0, 0);                           \
+        lo1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[Q], Y2, lo1, 0, 0, 0);                           \
+        lo0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2[Q], X0, lo0, 0, 0, 0);                           \
+        lo1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2[Q], Y0, lo1, 0, 0, 0);                           \
+        lo0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1[Q], X1, lo0, 0, 0, 0);                           \
+        lo1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1[Q], Y1, lo1, 0, 0, 0);                           \
+        lo0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[Q], X1, lo0, 0, 0, 0);                           \
+        lo1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[Q], Y1, lo1, 0, 0, 0);                           \
+        lo0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1[Q], X0, lo0, 0, 0, 0);                           \
+        lo1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1[Q], Y0, lo1, 0, 0, 0);                           \
+        hi0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[Q], X0, hi0, 0, 0, 0);                           \
+        hi1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[Q], Y0, hi1, 0, 0, 0)
+        if constexpr (KS == 2) {
+            // k-split: this wave's four k-steps (k = 128 kh + 32 q ..), the fragments single-buffered: four waves per
+            // SIMD cover the read latency that the two-wave form hides with its second fragment set (24 VGPRs that
+            // the 128-register budget does not have)
+            const unsigned ab = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)(lds + bb * ABYTES) +
+                                i * PITCH + 16 * g + 256 * kh;
+            u32x4 fx[3], fy[3];
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#define B3_LOADQ1(Q)                                                                                     \
+            asm volatile("ds_read_b128 %0, %6 offset:%7\n\tds_read_b128 %1, %6 offset:%8\n\t"             \
+                         "ds_read_b128 %2, %6 offset:%9\n\tds_read_b128 %3, %6 offset:%10\n\t"            \
+                         "ds_read_b128 %4, %6 offset:%11\n\tds_read_b128 %5, %6 offset:%12"               \
+                         : "=&v"(fx[0]), "=&v"(fx[1]), "=&v"(fx[2]), "=&v"(fy[0]), "=&v"(fy[1]), "=&v"(fy[2]) \
+                         : "v"(ab), "i"(64 * (Q)), "i"(64 * (Q) + 512), "i"(64 * (Q) + 1024),            \
+                           "i"(64 * (Q) + 16 * PITCH), "i"(64 * (Q) + 16 * PITCH + 512),                  \
+                           "i"(64 * (Q) + 16 * PITCH + 1024)                                             \
+                         : "memory")
+#pragma unroll
+            for (int q = 0; q < KQ; ++q) {
+                switch (q) {      // the offsets are immediates: one asm per k-step
+                    case 0: B3_LOADQ1(0); break;
+                    case 1: B3_LOADQ1(1); break;
+                    case 2: B3_LOADQ1(2); break;
+                    default: B3_LOADQ1(3); break;
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)"
+                             : "+v"(fx[0]), "+v"(fx[1]), "+v"(fx[2]), "+v"(fy[0]), "+v"(fy[1]), "+v"(fy[2])::"memory");
+                const bf16x8 x0 = __builtin_bit_cast(bf16x8, fx[0]), x1 = __builtin_bit_cast(bf16x8, fx[1]),
+                             x2 = __builtin_bit_cast(bf16x8, fx[2]);
+                const bf16x8 y0 = __builtin_bit_cast(bf16x8, fy[0]), y1 = __builtin_bit_cast(bf16x8, fy[1]),
+                             y2 = __builtin_bit_cast(bf16x8, fy[2]);
+                B3_MFMAQ(q, x0, x1, x2, y0, y1, y2);
+            }
+#undef B3_LOADQ1
+            acc[0] = hi0 + lo0;
+            acc[1] = hi1 + lo1;
+            return;
+        }
         // Fragment reads in inline asm, one k-step ahead of the MFMAs that use them, each k-step's MFMAs behind an
         // s_waitcnt lgkmcnt(6) that "defines" its six fragments (so the MFMAs cannot be scheduled above it): the
         // compiler's own waits were lgkmcnt(0) right after the next k-step's loads, exposing the LDS latency once
@@ -2258,7 +2324,7 @@ __global__ __launch_bounds__(512) void rowgemm256_b3_kernel(RowGemmP p, int n_ra
                      : "memory")
         B3_LOADQ(0, 0);
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
+        for (int q = 0; q < KQ; ++q) {
             const int S = q & 1;
             if (q + 1 < 8) {
                 switch (q) {      // the offsets are immediates: one asm per k-step
@@ -2296,9 +2362,79 @@ __global__ __launch_bounds__(512) void rowgemm256_b3_kernel(RowGemmP p, int n_ra
             hi1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[q], y0, hi1, 0, 0, 0);
         }
 #undef B3_LOADQ
+#undef B3_MFMAQ
         acc[0] = hi0 + lo0;
         acc[1] = hi1 + lo1;
     };
+
+    // KS = 2 (gathered forward): 16 waves, wave (column group c, k half h) = wid c + 8h, so a SIMD holds two column
+    // groups x both k halves, four waves.  The k-high wave of a pair stages and converts the A rows (4, as the
+    // two-wave form) and hands its partial (hi + lo of k 128..255) over through the pair's 2-KB exchange; the k-low
+    // wave owns the indices, slabs and coefficients and runs the epilogue of tile t-1 before its MFMAs of tile t:
+    // C = act((acc(k 0..127) + acc(k 128..255)) + combine), always in that order.  Two barriers per tile order
+    // the one exchange buffer: the mid barrier stands between the k-low wave's read of partial(t-1) (top of
+    // iteration t) and the k-high wave's store of partial(t) (after it), the end barrier between that store, the
+    // converted A(t+1), and their readers of iteration t+1.  The vmcnt(0) waits below are exact counts: nothing the
+    // wave issued is younger than what it waits for (k-high: its 4 A rows; k-low: slabs(t-1) and idx(t)).
+    if constexpr (KS == 2) {
+        f32x4* xw = reinterpret_cast<f32x4*>(lds + XOFF + wave * XB) + lane;
+        f32x4 acc[2];
+        int b = 0;
+        if (kh) {
+            dma_A(t_beg, 0);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            convert(0);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __syncthreads();
+            for (long long t = t_beg; t < t_end; ++t) {
+                const int nA = dma_A(t + 1, b ^ 1);
+                mfma_tile(b, acc);
+                if (nA) {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    convert(b ^ 1);
+                }
+                __builtin_amdgcn_s_barrier();           // the partner has read partial(t-1)
+                asm volatile("" ::: "memory");
+                xw[0] = acc[0];
+                xw[64] = acc[1];
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+                b ^= 1;
+            }
+        } else {
+            dma_idx(t_beg);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            dma_slabs(t_beg);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            dma_idx(t_beg + 1);
+            __syncthreads();
+            for (long long t = t_beg; t < t_end; ++t) {
+                if (t > t_beg) {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // slabs(t-1), idx(t)
+                    acc[0] = acc[0] + xw[0];
+                    acc[1] = acc[1] + xw[64];
+                    epilogue(t - 1, acc);
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    dma_slabs(t);
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    dma_idx(t + 1);
+                }
+                mfma_tile(b, acc);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+                b ^= 1;
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            acc[0] = acc[0] + xw[0];
+            acc[1] = acc[1] + xw[64];
+            epilogue(t_end - 1, acc);
+        }
+        return;
+    }
 
     // prologue: indices, A and slabs of t_beg; A converted; indices of t_beg + 1
     dma_idx(t_beg);
@@ -4387,11 +4523,11 @@ void launch_b3(hipStream_t st, RowGemmP p, int nv, bool aux, bool bc) {
     nr = (nr + 7) / 8 * 8;
     const int n_ranges = (int)nr;
     if (p.accumulate) p.aux = p.C;
-    const dim3 g((unsigned)(2 * nr)), blk(512);
+    const dim3 g((unsigned)(2 * nr)), blk(512), blk2(1024);      // k-split gathered forward: 16 waves
     if (bc && aux) hipLaunchKernelGGL((rowgemm256_b3_kernel<0, true, true>), g, blk, 0, st, p, n_ranges);
     else if (bc) hipLaunchKernelGGL((rowgemm256_b3_kernel<0, false, true>), g, blk, 0, st, p, n_ranges);
-    else if (nv == 1) hipLaunchKernelGGL((rowgemm256_b3_kernel<1, false>), g, blk, 0, st, p, n_ranges);
-    else if (nv == 2) hipLaunchKernelGGL((rowgemm256_b3_kernel<2, false>), g, blk, 0, st, p, n_ranges);
+    else if (nv == 1) hipLaunchKernelGGL((rowgemm256_b3_kernel<1, false, false, 2>), g, blk2, 0, st, p, n_ranges);
+    else if (nv == 2) hipLaunchKernelGGL((rowgemm256_b3_kernel<2, false, false, 2>), g, blk2, 0, st, p, n_ranges);
     else if (aux) hipLaunchKernelGGL((rowgemm256_b3_kernel<0, true>), g, blk, 0, st, p, n_ranges);
     else hipLaunchKernelGGL((rowgemm256_b3_kernel<0, false>), g, blk, 0, st, p, n_ranges);
 }

@@ -26,8 +26,9 @@ SYMBOLS = {
               "tail_bwd_gemm": "rowgemm256_v3_kernel<0, true, false, true, false, false,",
               "tail_dS_tn": "gemm_tn256_x3_kernel<"},
     # bf16x3 operands (ABI 7): the column-half row GEMM and the transposed-read TN
-    "bf16x3": {"tail_fwd_gemm": "rowgemm256_b3_kernel<2, false, false>",
-               "tail_bwd_gemm": "rowgemm256_b3_kernel<0, true, false>",
+    # (rowgemm256_b3_kernel<NV, AUX, BC, KS>: the gathered forward is the k-split form, KS = 2)
+    "bf16x3": {"tail_fwd_gemm": "rowgemm256_b3_kernel<2, false, false, 2>",
+               "tail_bwd_gemm": "rowgemm256_b3_kernel<0, true, false, 1>",
                "tail_dS_tn": "gemm_tn256_b3_kernel",
                "tail_bwd_sigma_tn": "sigma_tn_b3_kernel"},           # round 6: the fused pass (ABI 12)
     "exact": {"tail_fwd_gemm": "rowgemm256_v3_kernel<2, false, true, false, false, false, false, false>",
