@@ -210,7 +210,10 @@ int iddgcn_combine_planes_f32(void* stream, int M, int d, int R, const float* Y,
  *   g = scale * dloss_e/dp (0 where p is clipped), ds = g p (1-p)
  *   ds_out[e] = ds;  do_out[e] = ds*rho*a * b*(1-b)
  *   drel_slab[blk][r][:] += ds*a*b ; loss_slab[blk] += loss_e
- * n_blocks from iddgcn_distmult_blocks(); slabs hold n_blocks*R*D and n_blocks floats. */
+ * n_blocks from iddgcn_distmult_blocks(); slabs hold n_blocks*R*D and n_blocks floats.
+ * T == 0: nothing is launched and NOTHING is written, the slabs included: the caller must not reduce them (a
+ * training step scores through iddgcn_distmult_bce_heads_f32, which always writes its n_blocks partials:
+ * zeros for heads without edges and for n_nodes == 0). */
 int iddgcn_distmult_blocks(long long T);
 int iddgcn_distmult_bce_f32(void* stream, long long T, int d, int R,
                             const float* Xh, const int* h_idx, const float* Xt, const int* t_idx,
