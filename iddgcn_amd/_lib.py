@@ -1,5 +1,5 @@
 """ctypes binding of libiddgcn_hip.so (C-ABI declared in include/iddgcn.h, iddgcn_graph.h,
-iddgcn_similarity.h and iddgcn_sampling.h).
+iddgcn_similarity.h, iddgcn_sampling.h and iddgcn_screen.h).
 
 The product path has no CPU fallback: if the shared library is missing, was
 built for another ABI version or from other sources than the tree beside it
@@ -17,7 +17,7 @@ LIB_PATH = PRODUCT_LIB
 # product loads PRODUCT_LIB
 if os.environ.get("IDDGCN_LIB"):
     LIB_PATH = os.environ["IDDGCN_LIB"]
-ABI_VERSION = 12
+ABI_VERSION = 13
 ROWGEMM_BATCH = 25          # IDDGCN_ROWGEMM_BATCH: entries per iddgcn_rowgemm_batched_f32 call
 
 ACT_NONE, ACT_SIGMOID, ACT_DSIGMOID = 0, 1, 2
@@ -53,6 +53,8 @@ class TnArgs(ctypes.Structure):
 
 
 TN_BATCH = 4
+SCREEN_TAIL, SCREEN_HEAD = 0, 1                   # include/iddgcn_screen.h IDDGCN_SCREEN_*
+TOPK_MAX = 64
 
 
 # name -> (restype, argtypes)
@@ -116,6 +118,9 @@ SIGNATURES = {
     "iddgcn_similarity_workspace": (cll, [ci, ci]),
     "iddgcn_similarity_pairs": (ci, [vp, ci, ci, vp, ctypes.c_double, vp, cll, vp, cll, vp, vp, cll]),
     "iddgcn_similarity_triples": (ci, [vp, cll, ci, ci, cll, vp, vp]),
+    # include/iddgcn_screen.h (ABI 13)
+    "iddgcn_screen_chain_f32": (ci, [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, cll, cll, vp, cll, vp, vp, vp, vp, vp]),
+    "iddgcn_rank_topk_f32": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

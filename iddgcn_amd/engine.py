@@ -452,6 +452,9 @@ class Engine:
             return self._forward_rows(P, adj, ed, ws, train)
         N, R, D, T = self.N, self.R, self.D, ed.T
         E = P["E"]
+        # NOTE: _node_tables (all-candidate ranking) repeats the node-level launches of the unsharded path below —
+        # AE, P, ES1, W^l, X^l — and must follow any change to them (tests/test_gpu_ranking.py compares its tables
+        # with this forward's bitwise).
         # every GEMM call carries this engine's operand precision: pn for the plain node-level projections, pr for
         # the other row GEMMs
         pn = dict(precision=self.proj_gemm)
@@ -920,6 +923,144 @@ class Engine:
         ws = self.workspace(ed.T, False)
         self.forward(params, adj, ed, ws, False)
         return (ed.unsort(ws.p), ed.unsort(ws.s)) if logits else ed.unsort(ws.p)
+
+    # -- all-candidate ranking ----------------------------------------------------
+    def _node_tables(self, P, adj, ws):
+        """The node-level part of forward() alone (unsharded engine): AE_r, P_r^l, ES1, the dynamic weights W^l and
+        the head chain X^l, everything a scored edge's tail chain and DistMult read.  ES1 keeps E·S^1 (at R > 2,
+        D = 256 forward() reuses it as scratch for X^{l-1}·S^l; here the tail side reads it afterwards, so that
+        product goes through a table of its own)."""
+        N, R, D = self.N, self.R, self.D
+        E = P["E"]
+        pn, pr = dict(precision=self.proj_gemm), dict(precision=self.row_gemm)
+        ops.spmm_csr(adj.fwd_ptr, adj.fwd_col, adj.fwd_val, E, ws.AE, R, N)
+        proj = [(ws.AE[r], P[f"K{l + 1}"][r], ws.P[l, r], pn) for l in range(NUM_LAYERS) for r in range(R)]
+        proj.append((E, P["S1"], ws.ES1, pn))
+        for i in range(0, len(proj), L.ROWGEMM_BATCH):
+            ops.rowgemm_batched(proj[i:i + L.ROWGEMM_BATCH])
+        ops.alpha_fwd(E, P["Wa1"], P["ba1"], ws.Ssm[0], ws.W[0])
+        ops.combine(ws.ES1, ws.W[0], ws.P[0], ws.X[0])
+        for l in (1, 2):
+            S = P[f"S{l + 1}"]
+            ops.alpha_fwd(ws.X[l - 1], P[f"Wa{l + 1}"], P[f"ba{l + 1}"], ws.Ssm[l], ws.W[l])
+            if R > 2 and D == 256:
+                if getattr(ws, "xs", None) is None:
+                    ws.xs = torch.empty(N, D, dtype=torch.float32, device=self.device)
+                ops.rowgemm(ws.X[l - 1], S, ws.xs, **pr)
+                ops.combine(ws.xs, ws.W[l], ws.P[l], ws.X[l])
+            else:
+                ops.rowgemm(ws.X[l - 1], S, ws.X[l], coef=ws.W[l], V=ws.P[l], v_rel_stride=N * D,
+                            act=L.ACT_SIGMOID, **pr)
+
+    def _screen_layered(self, P, ws, h, r, t, s_out):
+        """The tail chain and DistMult of forward() over a dense block of scored edges given by device index arrays
+        (no sort, no segments): the same edge kernels and launch order as forward()'s per-edge part."""
+        N, D, T = self.N, self.D, h.shape[0]
+        pl = self.use_planes
+        xt = [ws.xt[l][:T] for l in range(NUM_LAYERS)]
+        we = [ws.Wedge[l][:T] for l in range(NUM_LAYERS)]
+        ops.gather_rows(ws.W[0], h, we[0])
+        ops.combine(ws.ES1, we[0], ws.P[0], xt[0], y_idx=t, v_idx=t, planes_out=pl)
+        for l in (1, 2):
+            ops.gather_rows(ws.W[l], h, we[l])
+            ops.rowgemm(xt[l - 1], P[f"S{l + 1}"], xt[l], coef=we[l], V=ws.P[l], v_idx=t, v_rel_stride=N * D,
+                        act=L.ACT_SIGMOID, planes=(L.PLANES_A | (L.PLANES_C if l == 1 else 0)) if pl else 0,
+                        precision=self.edge_gemm)
+        ops.distmult_bce(ws.X[2], h, xt[2], r, P["rel"], p_out=ws.p[:T], s_out=s_out)
+
+    def rank_candidates(self, params, adj, queries, side="tail", k=10, filter_csr=None, return_scores=False,
+                        max_edges=1 << 22, fused=None):
+        """Score every entity as the partner of each query and rank the query's own partner among them.
+
+        ``queries``: (Q, 3) triples (h, r, t).  side "tail" scores (h, r, c) for every c in [0, N) with target t;
+        "head" scores (c, r, t) with target h.  The score is the pre-sigmoid DistMult logit predict() returns for
+        that triple.  ``filter_csr`` = (fptr (Q + 1), fidx): candidate ids left out of query q, ascending and unique
+        per query (utils.filter_csr builds it from known positives); the target is exempt.  The node tables are
+        computed once; the queries then run in chunks of at most ``max_edges // N`` (at least 1).  ``fused``: None
+        picks the fused kernel (ops.screen_chain) when D <= 64 with fp32 features, False forces the layered path (the
+        edge kernels of forward() over a dense edge block; every width and mode), True demands the fused kernel.
+
+        Returns a dict of device tensors: ``greater`` / ``equal`` (Q,) int32 — the non-filtered candidates other than
+        the target scoring above / exactly the target's logit —, ``topk_idx`` (Q, k) int32 and ``topk_val`` (Q, k) —
+        the k best non-filtered candidates, descending, ties by ascending id, padded with -1 / -inf — and, with
+        ``return_scores``, ``scores`` (Q, N)."""
+        if side not in ("tail", "head"):
+            raise ValueError(f"side must be 'tail' or 'head', got {side!r}")
+        if not 1 <= int(k) <= L.TOPK_MAX:
+            raise ValueError(f"k must be in [1, {L.TOPK_MAX}], got {k}")
+        if self.node_shard is not None or self.spmm_shard is not None or self.row_shard is not None:
+            raise L.IddgcnError("rank_candidates: not available on an Engine with node_shard / spmm_shard / row_shard "
+                                "set")
+        N, R, D, dev = self.N, self.R, self.D, self.device
+        k = int(k)
+        can_fuse = D <= 64 and self.features == "f32"
+        if fused is None:
+            fused = can_fuse and self.fused_screen_default
+        elif fused and not can_fuse:
+            raise L.IddgcnError("rank_candidates: the fused kernel takes D <= 64 with fp32 features")
+        q = np.asarray(queries.cpu() if isinstance(queries, torch.Tensor) else queries).astype(np.int64)
+        if q.ndim != 2 or q.shape[1] != 3:
+            raise L.IddgcnError(f"queries must be (Q, 3), got {q.shape}")
+        Q = q.shape[0]
+        if Q and (min(q[:, 0].min(), q[:, 2].min()) < 0 or max(q[:, 0].max(), q[:, 2].max()) >= N):
+            raise L.IddgcnError("query entity index out of range [0, num_entities)")
+        if Q and (q[:, 1].min() < 0 or q[:, 1].max() >= R):
+            raise L.IddgcnError("query relation index out of range [0, num_relations)")
+        i32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=dev)  # noqa: E731
+        node = i32(q[:, 0] if side == "tail" else q[:, 2])
+        target = i32(q[:, 2] if side == "tail" else q[:, 0])
+        rel = i32(q[:, 1])
+        fptr = fidx = None
+        if filter_csr is not None:
+            fp = np.asarray(filter_csr[0].cpu() if isinstance(filter_csr[0], torch.Tensor) else filter_csr[0])
+            fi = np.asarray(filter_csr[1].cpu() if isinstance(filter_csr[1], torch.Tensor) else filter_csr[1])
+            fp, fi = fp.astype(np.int64).ravel(), fi.astype(np.int64).ravel()
+            if fp.shape != (Q + 1,) or fp[0] != 0 or fp[-1] != len(fi) or (np.diff(fp) < 0).any():
+                raise L.IddgcnError("filter_csr: fptr must be (Q + 1,), ascending from 0 to len(fidx)")
+            if len(fi):
+                inner = np.ones(len(fi), bool)
+                inner[fp[:-1][fp[:-1] < len(fi)]] = False          # a row's first entry has no predecessor
+                if fi.min() < 0 or fi.max() >= N or (np.diff(fi)[inner[1:]] <= 0).any():
+                    raise L.IddgcnError("filter_csr: fidx must lie in [0, num_entities), ascending and unique per query")
+            fptr, fidx = i32(fp), i32(fi)
+        self.finish_pending()
+        chunk = max(1, int(max_edges) // N)
+        out = {"greater": torch.empty(Q, dtype=torch.int32, device=dev),
+               "equal": torch.empty(Q, dtype=torch.int32, device=dev),
+               "topk_idx": torch.empty(Q, k, dtype=torch.int32, device=dev),
+               "topk_val": torch.empty(Q, k, dtype=torch.float32, device=dev)}
+        if return_scores:
+            out["scores"] = torch.empty(Q, N, dtype=torch.float32, device=dev)
+        if Q == 0:
+            return out
+        if fused:
+            ws = next((w for (_, tr), w in self._ws.items() if not tr), None) or self.workspace(1, False)
+        else:
+            if min(chunk, Q) * N > np.iinfo(np.int32).max:
+                raise L.IddgcnError("too many scored edges for int32 indexing")
+            ws = self.workspace(min(chunk, Q) * N, False)
+            cand = torch.arange(N, dtype=torch.int32, device=dev)
+        self._node_tables(params, adj, ws)
+        sbuf = None if return_scores else torch.empty(min(chunk, Q), N, dtype=torch.float32, device=dev)
+        for q0 in range(0, Q, chunk):
+            q1 = min(q0 + chunk, Q)
+            s = out["scores"][q0:q1] if return_scores else sbuf[:q1 - q0]
+            if fused:
+                ops.screen_chain(node[q0:q1], rel[q0:q1], ws.ES1, ws.P, ws.W, ws.X[2], params["S2"], params["S3"],
+                                 params["rel"], s, side)
+            else:
+                # the dense edge block (q, c) -> row (q - q0) N + c, built on the device
+                qn = node[q0:q1].repeat_interleave(N)
+                cn = cand.repeat(q1 - q0)
+                h, t = (qn, cn) if side == "tail" else (cn, qn)
+                self._screen_layered(params, ws, h, rel[q0:q1].repeat_interleave(N), t, s.view(-1))
+            ops.rank_topk(s, target[q0:q1], k, None if fptr is None else fptr[q0:q1 + 1], fidx,
+                          out["greater"][q0:q1], out["equal"][q0:q1], out["topk_idx"][q0:q1], out["topk_val"][q0:q1])
+        return out
+
+    # rank_candidates(fused=None) takes the fused kernel at D <= 64 (tools/screen_bench.py, DESIGN.md: all-candidate
+    # ranking)
+    fused_screen_default = True
 
     def layer_outputs(self, ed, rows=None):
         """After a predict() forward: the per-edge layer outputs (x_h^l, x_t^l), l = 1..3, of the

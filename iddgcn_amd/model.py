@@ -420,6 +420,36 @@ class IDDGCN_Model:
         _, s = eng.predict(self._params, dadj, ed, logits=True)
         return s.detach().cpu().numpy().reshape(1, -1)
 
+    def rank_candidates(self, x, side="tail", k=10, filter_triples=None, return_scores=False, **kw):
+        """Rank every entity as the partner of each triple of ``x`` (the list predict takes): side "tail" scores
+        (h, r, c) for all c with target t, "head" scores (c, r, t) with target h, by the logit predict_logits
+        returns.  ``filter_triples`` (F, 3): known positives; a tail-side query leaves out the c with (h, r, c)
+        among them (head side symmetric), the target itself excepted.  ``kw`` goes to Engine.rank_candidates
+        (max_edges, fused).  Returns numpy arrays: rank_optimistic = 1 + #better, rank_pessimistic = that + #tied,
+        rank (their mean), topk_entities / topk_logits / topk_probs (Q, k) (padded with -1 / -inf / 0) and, with
+        ``return_scores``, scores (Q, N)."""
+        if side not in ("tail", "head"):
+            raise ValueError(f"side must be 'tail' or 'head', got {side!r}")
+        if not 1 <= int(k) <= L.TOPK_MAX:
+            raise ValueError(f"k must be in [1, {L.TOPK_MAX}], got {k}")
+        from .utils import filter_csr
+        eng = self._device_state()
+        h, r, t, adj = self._unpack(x)
+        dadj = self._adjacency(adj)
+        q = np.stack([h, r, t], 1).astype(np.int64)
+        csr = None if filter_triples is None else filter_csr(q, side, filter_triples, self.num_entities)
+        o = eng.rank_candidates(self._params, dadj, q, side=side, k=int(k), filter_csr=csr,
+                                return_scores=return_scores, **kw)
+        probs = torch.sigmoid(o["topk_val"])
+        o = {name: v.detach().cpu().numpy() for name, v in o.items()}
+        opt = 1 + o["greater"].astype(np.int64)
+        pes = opt + o["equal"].astype(np.int64)
+        out = {"rank_optimistic": opt, "rank_pessimistic": pes, "rank": (opt + pes) / 2.0,
+               "topk_entities": o["topk_idx"], "topk_logits": o["topk_val"], "topk_probs": probs.cpu().numpy()}
+        if return_scores:
+            out["scores"] = o["scores"]
+        return out
+
     def __call__(self, x, training=False):
         return torch.as_tensor(self.predict(x))
 

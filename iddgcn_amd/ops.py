@@ -722,3 +722,85 @@ def f32_to_planes(x):
     lo = (xs - hi.float()).half()
     rows = x.shape[0]
     return torch.stack([hi.view(rows, -1, 32), lo.view(rows, -1, 32)], 2).reshape(rows, -1).contiguous().view(torch.float32)
+
+
+# -- all-candidate ranking (include/iddgcn_screen.h) ---------------------------------------------
+_SIDES = {"tail": L.SCREEN_TAIL, "head": L.SCREEN_HEAD, L.SCREEN_TAIL: L.SCREEN_TAIL, L.SCREEN_HEAD: L.SCREEN_HEAD}
+
+
+def _side(side):
+    if side not in _SIDES:
+        raise L.IddgcnError(f"side must be 'tail' or 'head', got {side!r}")
+    return _SIDES[side]
+
+
+def screen_chain(q_node, q_rel, ES1, P, W, X3, S2, S3, rel, s, side="tail"):
+    """s[q, c] = the pre-sigmoid DistMult logit of query q against every candidate c in [0, N): the three-layer
+    tail chain and DistMult in one kernel (iddgcn_screen_chain_f32; D in {32, 64}, fp32 tables).  side "tail":
+    (q_node[q], q_rel[q], c); "head": (c, q_rel[q], q_node[q]).  P: (3, R, N, D) and W: (3, N, R) views with
+    contiguous rows (the engine's ws.P / ws.W), ES1, X3 (N, D), S2, S3 (D, D), rel (R, D), s (Q, N)."""
+    Q, N = s.shape
+    R, D = rel.shape
+    _req(s, _F32, (Q, N), "s")
+    _idx_ok(q_node, Q, N, "q_node")
+    _idx_ok(q_rel, Q, R, "q_rel")
+    for t, shape, nm in ((ES1, (N, D), "ES1"), (X3, (N, D), "X3"), (S2, (D, D), "S2"), (S3, (D, D), "S3"),
+                         (rel, (R, D), "rel")):
+        _req(t, _F32, shape, nm)
+    for t, shape, nm in ((P, (3, R, N, D), "P"), (W, (3, N, R), "W")):
+        if t is None or not t.is_cuda or t.dtype != _F32:
+            raise L.IddgcnError(f"{nm} must be an fp32 GPU tensor (no CPU fallback)")
+        if tuple(t.shape) != shape or t.stride(-1) != 1 or t.stride(-2) != shape[-1]:
+            raise L.IddgcnError(f"{nm} must be {shape} with contiguous rows")
+    if P.stride(1) < N * D:
+        raise L.IddgcnError("screen_chain: the relations of P overlap")
+    # rows of ES1 and P are read as 16-byte vectors
+    if (ES1.data_ptr() | P.data_ptr()) & 15 or P.stride(0) % 4 or P.stride(1) % 4:
+        raise L.IddgcnError("screen_chain: ES1 / P must be 16-byte aligned, P's layer and relation strides "
+                            "multiples of 4 floats")
+    L.check(L.lib().iddgcn_screen_chain_f32(_stream(), Q, N, D, R, _side(side), _ptr(q_node), _ptr(q_rel), _ptr(ES1),
+                                            _ptr(P), P.stride(0), P.stride(1), _ptr(W), W.stride(0), _ptr(X3),
+                                            _ptr(S2), _ptr(S3), _ptr(rel), _ptr(s)), "screen_chain")
+
+
+def rank_topk(s, target, k, fptr=None, fidx=None, greater=None, equal=None, topk_idx=None, topk_val=None):
+    """Per-query selection over s (Q, N) (iddgcn_rank_topk_f32): greater / equal = the non-filtered candidates
+    c != target[q] scoring above / exactly s[q, target[q]] (0 where target is -1), and the k best non-filtered
+    candidates, descending by value, ties by ascending id, padded with -1 / -inf.  fptr (Q + 1), fidx: the
+    filter as CSR, candidate ids ascending and unique per query; the target is exempt.  s is not modified.
+    Returns (greater, equal, topk_idx, topk_val), allocated when not given."""
+    if s.dim() != 2:
+        raise L.IddgcnError("rank_topk: s must be (Q, N)")
+    Q, N = s.shape
+    k = int(k)
+    if not 1 <= k <= L.TOPK_MAX:
+        raise L.IddgcnError(f"rank_topk: k must be in [1, {L.TOPK_MAX}]")
+    dev = s.device
+    _req(s, _F32, (Q, N), "s")
+    _req(target, _I32, (Q,), "target")
+    if CHECK_INDEX_RANGES and Q:
+        lo, hi = int(target.min()), int(target.max())
+        if lo < -1 or hi >= N:
+            raise L.IddgcnError(f"target: index out of range [-1, {N}): min {lo}, max {hi}")
+    if (fptr is None) != (fidx is None):
+        raise L.IddgcnError("rank_topk: fptr and fidx go together")
+    if fptr is not None:
+        _req(fptr, _I32, (Q + 1,), "fptr")
+        _req(fidx, _I32, None, "fidx")
+        if CHECK_INDEX_RANGES and Q:
+            p = fptr.cpu()
+            if int(p[0]) < 0 or bool((p[1:] < p[:-1]).any()) or int(p[-1]) > fidx.numel():
+                raise L.IddgcnError("rank_topk: fptr must ascend within [0, len(fidx)]")
+        if fidx.numel() == 0:
+            fptr = fidx = None
+    greater = torch.empty(Q, dtype=_I32, device=dev) if greater is None else greater
+    equal = torch.empty(Q, dtype=_I32, device=dev) if equal is None else equal
+    topk_idx = torch.empty(Q, k, dtype=_I32, device=dev) if topk_idx is None else topk_idx
+    topk_val = torch.empty(Q, k, dtype=_F32, device=dev) if topk_val is None else topk_val
+    _req(greater, _I32, (Q,), "greater")
+    _req(equal, _I32, (Q,), "equal")
+    _req(topk_idx, _I32, (Q, k), "topk_idx")
+    _req(topk_val, _F32, (Q, k), "topk_val")
+    L.check(L.lib().iddgcn_rank_topk_f32(_stream(), Q, N, k, _ptr(s), _ptr(target), _ptr(fptr), _ptr(fidx),
+                                         _ptr(greater), _ptr(equal), _ptr(topk_idx), _ptr(topk_val)), "rank_topk")
+    return greater, equal, topk_idx, topk_val

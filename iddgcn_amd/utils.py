@@ -23,6 +23,31 @@ def get_y_true(X_test_pos, X_test_rule):
     return (merged["_merge"] == "both").astype(int).values
 
 
+def filter_csr(queries, side, filter_triples, num_entities):
+    """The filtered-ranking setting as CSR over the queries (Engine.rank_candidates ``filter_csr``): for a tail-side
+    query (h, r, t) the candidates c with (h, r, c) among ``filter_triples`` (F, 3), for a head-side query the c with
+    (c, r, t) among them; ascending and unique per query.  The query's own target may be listed: the ranking
+    exempts it.  Returns (fptr (Q + 1,) int32, fidx int32)."""
+    if side not in ("tail", "head"):
+        raise ValueError(f"side must be 'tail' or 'head', got {side!r}")
+    q = np.asarray(queries, dtype=np.int64).reshape(-1, 3)
+    f = np.asarray(filter_triples, dtype=np.int64).reshape(-1, 3)
+    n = int(num_entities)
+    fixed, cand = (0, 2) if side == "tail" else (2, 0)
+    # sorted unique (relation, fixed node, candidate) keys: one query's candidates are a contiguous, ascending run
+    keys = np.unique((f[:, 1] * n + f[:, fixed]) * n + f[:, cand])
+    qk = (q[:, 1] * n + q[:, fixed]) * n
+    lo, hi = np.searchsorted(keys, qk, side="left"), np.searchsorted(keys, qk + n, side="left")
+    fptr = np.zeros(len(q) + 1, np.int64)
+    np.cumsum(hi - lo, out=fptr[1:])
+    if fptr[-1] > np.iinfo(np.int32).max:
+        raise ValueError("filter too large for int32 offsets")
+    fidx = np.empty(int(fptr[-1]), np.int64)
+    for i in np.flatnonzero(hi > lo):
+        fidx[fptr[i]:fptr[i + 1]] = keys[lo[i]:hi[i]] - qk[i]
+    return fptr.astype(np.int32), fidx.astype(np.int32)
+
+
 def synthetic_graph(num_nodes, num_relations, num_edges, seed=0, mut_frac=661 / 845):
     """Seeded synthetic mutation–drug graph.
 

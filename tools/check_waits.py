@@ -2,7 +2,8 @@
 LDS-DMA kernels of libiddgcn_hip, with the instruction each one guards.  A compiler vmcnt wait inside a
 main loop drains every DMA in flight (A tiles, slabs, stores) and defeats the software pipeline, so the
 hot kernels should show none there except in rarely taken branches (e.g. `accumulate` loads).
-usage: python tools/check_waits.py [--src file.hip] [kernel-substring ...]   (compiles iddgcn_hip.hip to gfx950 asm)
+usage: python tools/check_waits.py [--src file.hip] [kernel-substring ...]   (compiles iddgcn_hip.hip to gfx950 asm;
+       --src iddgcn_amd/csrc/screen.hip for the ranking kernels, or any other translation unit of the library)
 """
 import os
 import re
