@@ -1,5 +1,5 @@
 """ctypes binding of libiddgcn_hip.so (C-ABI declared in include/iddgcn.h, iddgcn_graph.h,
-iddgcn_similarity.h, iddgcn_sampling.h and iddgcn_screen.h).
+iddgcn_similarity.h, iddgcn_sampling.h, iddgcn_screen.h and iddgcn_explain.h).
 
 The product path has no CPU fallback: if the shared library is missing, was
 built for another ABI version or from other sources than the tree beside it
@@ -121,6 +121,11 @@ SIGNATURES = {
     # include/iddgcn_screen.h (ABI 13)
     "iddgcn_screen_chain_f32": (ci, [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, cll, cll, vp, cll, vp, vp, vp, vp, vp]),
     "iddgcn_rank_topk_f32": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]),
+    # include/iddgcn_explain.h (batched explaiNE; added symbols only, the ABI version stays)
+    "iddgcn_explain_seeds_f32": (ci, [vp, ci, ci, ci, ci, vp, vp, vp, cf, vp, vp, cll, cll, vp, vp, cll, vp, cll,
+                                      vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "iddgcn_explain_row_grads_f32": (ci, [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "iddgcn_explain_topk_f32": (ci, [vp, ci, ci, vp, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -1,0 +1,509 @@
+// explain.hip — batched explaiNE for gfx950 (include/iddgcn_explain.h).
+//
+// The prediction of (h, r, t) reads A_r only through AE_r[h] and AE_r[t], so its gradient w.r.t. the adjacency values
+// lives in rows h and t alone.  Three kernels, none of them proportional to N or nnz:
+//
+// seeds_kernel: QT = 8 queries per workgroup.  The tail chain x^1..x^3 is recomputed from the node tables as in
+// screen_chain_kernel, then the backward of iddgcn_explain.h runs on 16 row vectors (head and tail of every query)
+// at once.  One d x d matrix (S^l or K^l_r) at a time is staged in LDS with rows padded to d + 1 floats, so that
+// both x·M (lanes along a row) and x·M^T (lanes down a column) read it without bank conflicts; every matrix element
+// read serves VPG vectors.  GH / GT accumulate in registers over the layers and are written once.  Exact fp32:
+// fmaf chains, four per dot product, (c0 + c1) + (c2 + c3).
+//
+// row_grads_kernel: one workgroup per query; GH, GT in LDS, one candidate (a stored entry of row h or t) per thread,
+// its dot product against E[col] in one thread (no cross-lane reduction, no atomics).
+//
+// topk_kernel: one workgroup per query over its candidate segment: rank_topk_kernel's passes (screen.hip), a bitonic
+// sort of 64-bit (value, entry id) keys in LDS merged into the running top 64.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "iddgcn.h"
+#include "iddgcn_explain.h"
+#include "iddgcn_screen.h"
+
+namespace xpl {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int MAX_R = 8;
+constexpr int NT = 256;            // 4 waves
+constexpr int QT = 8;              // queries per workgroup of seeds_kernel
+constexpr int NV = 2 * QT;         // row vectors: 2 qi = head of query qi, 2 qi + 1 = its tail
+
+// layer activations as the row GEMM's epilogue and screen_chain_kernel compute them
+__device__ __forceinline__ float sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+
+struct SeedP {
+    int Q, N, R;
+    const int* h; const int* r; const int* t;
+    float scale;
+    const float* ES1; const float* P; long long pls, prs;
+    const float* W; const float* Ssm; long long wls;
+    const float* X; long long xls;
+    const float* K[3]; const float* S[2]; const float* Wa[2]; const float* rel;
+    float* G; float* p;
+};
+
+// M (D rows of LD floats) <- a (D, D) row-major matrix
+template <int D>
+__device__ __forceinline__ void stage_matrix(float* M, const float* __restrict__ src) {
+#pragma unroll
+    for (int it = 0; it < D * D / NT; ++it) {
+        const int idx = it * NT + threadIdx.x;
+        M[(idx / D) * (D + 1) + idx % D] = src[idx];
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(NT) void seeds_kernel(const SeedP a) {
+    constexpr int LD = D + 1;
+    constexpr int GR = NT / D;         // thread groups of D lanes
+    constexpr int VPG = NV / GR;       // row vectors per group: 4 at D = 64, 2 at D = 32
+    __shared__ float M[D * LD];
+    __shared__ float act[3][NV][D];    // x^1..x^3 of every row vector
+    __shared__ float dx[NV][D];
+    __shared__ float dz[NV][D];
+    __shared__ float w[3][QT][MAX_R];
+    __shared__ float sm[3][QT][MAX_R];
+    __shared__ float dwv[NV][MAX_R];
+    __shared__ float da[QT][MAX_R];
+    __shared__ float du[QT][MAX_R];
+    __shared__ int node[NV];
+    __shared__ int qrel[QT];
+    const int tid = threadIdx.x;
+    const int R = a.R;
+    const int q0 = blockIdx.x * QT;
+    const int k = tid % D, grp = tid / D;
+
+    // queries past Q repeat the last one (computed, never stored)
+    if (tid < QT) {
+        const int q = q0 + tid < a.Q ? q0 + tid : a.Q - 1;
+        node[2 * tid] = a.h[q];
+        node[2 * tid + 1] = a.t[q];
+        qrel[tid] = a.r[q];
+    }
+    __syncthreads();
+    for (int idx = tid; idx < 3 * QT * R; idx += NT) {
+        const int l = idx / (QT * R), qi = (idx / R) % QT, r = idx % R;
+        const size_t o = (size_t)l * a.wls + (size_t)node[2 * qi] * R + r;
+        w[l][qi][r] = a.W[o];
+        sm[l][qi][r] = a.Ssm[o];
+    }
+    for (int idx = tid; idx < 3 * QT * D; idx += NT) {
+        const int l = idx / (QT * D), qi = (idx / D) % QT, c = idx % D;
+        act[l][2 * qi][c] = a.X[(size_t)l * a.xls + (size_t)node[2 * qi] * D + c];
+    }
+    __syncthreads();
+
+    // tail chain, layer 1: x^1 = sigmoid(ES1[t] + sum_r w_1r P^1_r[t]), r ascending
+    for (int idx = tid; idx < QT * D; idx += NT) {
+        const int qi = idx / D, c = idx % D;
+        const size_t row = (size_t)node[2 * qi + 1] * D + c;
+        float v = a.ES1[row];
+#pragma unroll
+        for (int r = 0; r < MAX_R; ++r)
+            if (r < R) v = fmaf(w[0][qi][r], a.P[r * a.prs + row], v);
+        act[0][2 * qi + 1][c] = sigmoid_fast(v);
+    }
+    // layers 2, 3: x^l = sigmoid(x^{l-1} S^l + sum_r w_lr P^l_r[t])
+    for (int l = 1; l < 3; ++l) {
+        stage_matrix<D>(M, a.S[l - 1]);
+        __syncthreads();
+        for (int idx = tid; idx < QT * D; idx += NT) {
+            const int qi = idx / D, c = idx % D;
+            const float* x = act[l - 1][2 * qi + 1];
+            float c4[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int i = 0; i < D; ++i) c4[(i >> 3) & 3] = fmaf(x[i], M[i * LD + c], c4[(i >> 3) & 3]);
+            float v = (c4[0] + c4[1]) + (c4[2] + c4[3]);
+            const size_t row = (size_t)node[2 * qi + 1] * D + c;
+            const float* Pl = a.P + l * a.pls;
+#pragma unroll
+            for (int r = 0; r < MAX_R; ++r)
+                if (r < R) v = fmaf(w[l][qi][r], Pl[r * a.prs + row], v);
+            act[l][2 * qi + 1][c] = sigmoid_fast(v);
+        }
+        __syncthreads();
+    }
+
+    // DistMult, the prediction and its seed: one thread per query, d ascending
+    if (tid < QT) {
+        const float* rl = a.rel + (size_t)qrel[tid] * D;
+        float s = 0.f;
+        for (int d = 0; d < D; ++d) s = fmaf(act[2][2 * tid][d] * rl[d], act[2][2 * tid + 1][d], s);
+        const float p = 1.0f / (1.0f + expf(-s));
+        da[tid][0] = a.scale * (p * (1.0f - p));
+        if (q0 + tid < a.Q) a.p[q0 + tid] = p;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < QT * D; idx += NT) {
+        const int qi = idx / D, c = idx % D;
+        const float gr = da[qi][0] * a.rel[(size_t)qrel[qi] * D + c];
+        dx[2 * qi][c] = gr * act[2][2 * qi + 1][c];
+        dx[2 * qi + 1][c] = gr * act[2][2 * qi][c];
+    }
+    __syncthreads();
+
+    float Gacc[VPG][MAX_R];
+#pragma unroll
+    for (int j = 0; j < VPG; ++j)
+#pragma unroll
+        for (int r = 0; r < MAX_R; ++r) Gacc[j][r] = 0.f;
+
+    for (int l = 2; l >= 0; --l) {
+        for (int idx = tid; idx < NV * D; idx += NT) {
+            const int v = idx / D, c = idx % D;
+            const float x = act[l][v][c];
+            dz[v][c] = dx[v][c] * (x * (1.0f - x));
+        }
+        __syncthreads();
+        // G_r += w_lr (dz K^l_r^T): lane k owns output column k of its group's VPG vectors
+#pragma unroll
+        for (int r = 0; r < MAX_R; ++r)
+            if (r < R) {
+                stage_matrix<D>(M, a.K[l] + (size_t)r * D * D);
+                __syncthreads();
+                float c4[VPG][4];
+#pragma unroll
+                for (int j = 0; j < VPG; ++j) c4[j][0] = c4[j][1] = c4[j][2] = c4[j][3] = 0.f;
+#pragma unroll 1
+                for (int i0 = 0; i0 < D; i0 += 32)
+#pragma unroll
+                    for (int ii = 0; ii < 32; ++ii) {
+                        const int i = i0 + ii;
+                        const float m = M[k * LD + i];
+#pragma unroll
+                        for (int j = 0; j < VPG; ++j)
+                            c4[j][(ii >> 3) & 3] = fmaf(dz[grp * VPG + j][i], m, c4[j][(ii >> 3) & 3]);
+                    }
+#pragma unroll
+                for (int j = 0; j < VPG; ++j) {
+                    const float acc = (c4[j][0] + c4[j][1]) + (c4[j][2] + c4[j][3]);
+                    Gacc[j][r] = fmaf(w[l][(grp * VPG + j) >> 1][r], acc, Gacc[j][r]);
+                }
+                __syncthreads();
+            }
+        if (l == 0) break;
+
+        // dw_r = <dzh, P^l_r[h]> + <dzt, P^l_r[t]>: per vector a butterfly over the D lanes of its group
+#pragma unroll
+        for (int j = 0; j < VPG; ++j) {
+            const int v = grp * VPG + j;
+            const float* Pl = a.P + l * a.pls + (size_t)node[v] * D + k;
+            const float z = dz[v][k];
+#pragma unroll
+            for (int r = 0; r < MAX_R; ++r)
+                if (r < R) {
+                    float part = z * Pl[r * a.prs];
+#pragma unroll
+                    for (int o = D / 2; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+                    if (k == 0) dwv[v][r] = part;
+                }
+        }
+        __syncthreads();
+        if (tid < QT * R) {
+            const int qi = tid / R, r = tid % R;
+            const float wv = w[l][qi][r];
+            da[qi][r] = (dwv[2 * qi][r] + dwv[2 * qi + 1][r]) * (wv * (1.0f - wv));
+        }
+        __syncthreads();
+        if (tid < QT * R) {
+            const int qi = tid / R, r = tid % R;
+            float sum = 0.f;
+            for (int i = 0; i < R; ++i) sum = fmaf(sm[l][qi][i], da[qi][i], sum);
+            du[qi][r] = sm[l][qi][r] * (da[qi][r] - sum);
+        }
+        // dx^{l-1} = dz S^l^T (+ du Walpha^l^T on the head side)
+        stage_matrix<D>(M, a.S[l - 1]);
+        __syncthreads();
+        {
+            float c4[VPG][4];
+#pragma unroll
+            for (int j = 0; j < VPG; ++j) c4[j][0] = c4[j][1] = c4[j][2] = c4[j][3] = 0.f;
+#pragma unroll 1
+            for (int i0 = 0; i0 < D; i0 += 32)
+#pragma unroll
+                for (int ii = 0; ii < 32; ++ii) {
+                    const int i = i0 + ii;
+                    const float m = M[k * LD + i];
+#pragma unroll
+                    for (int j = 0; j < VPG; ++j)
+                        c4[j][(ii >> 3) & 3] = fmaf(dz[grp * VPG + j][i], m, c4[j][(ii >> 3) & 3]);
+                }
+            const float* wa = a.Wa[l - 1] + (size_t)k * R;
+#pragma unroll
+            for (int j = 0; j < VPG; ++j) {
+                const int v = grp * VPG + j;
+                float acc = (c4[j][0] + c4[j][1]) + (c4[j][2] + c4[j][3]);
+                if ((v & 1) == 0) {
+#pragma unroll
+                    for (int r = 0; r < MAX_R; ++r)
+                        if (r < R) acc = fmaf(du[v >> 1][r], wa[r], acc);
+                }
+                dx[v][k] = acc;
+            }
+        }
+        __syncthreads();
+    }
+
+#pragma unroll
+    for (int j = 0; j < VPG; ++j) {
+        const int v = grp * VPG + j;
+        const int q = q0 + (v >> 1);
+        if (q < a.Q) {
+            float* g = a.G + ((size_t)q * 2 + (v & 1)) * R * D + k;
+#pragma unroll
+            for (int r = 0; r < MAX_R; ++r)
+                if (r < R) g[(size_t)r * D] = Gacc[j][r];
+        }
+    }
+}
+
+// ---- ragged SDDMM ----------------------------------------------------------------------------------------------
+struct RowP {
+    int N, R;
+    const int* h; const int* t; const int* row_ptr; const int* col; const long long* eoc;
+    const float* G; const float* E; const long long* qptr;
+    int* entry; float* grad;
+};
+
+template <int D>
+__global__ __launch_bounds__(NT) void row_grads_kernel(const RowP a) {
+    __shared__ __attribute__((aligned(16))) float Gs[2 * MAX_R * D];
+    __shared__ int seg_beg[2 * MAX_R];
+    __shared__ int seg_off[2 * MAX_R + 1];
+    const int tid = threadIdx.x;
+    const int q = blockIdx.x, R = a.R;
+    const int hh = a.h[q], tt = a.t[q];
+    const bool same = hh == tt;
+    const int ns = same ? R : 2 * R;
+    const float* g = a.G + (size_t)q * 2 * R * D;
+    for (int idx = tid; idx < R * D; idx += NT) {
+        const float g0 = g[idx], g1 = g[R * D + idx];
+        Gs[idx] = same ? g0 + g1 : g0;
+        Gs[R * D + idx] = g1;
+    }
+    if (tid == 0) {
+        int off = 0;
+        for (int s = 0; s < ns; ++s) {
+            const size_t row = (size_t)(s % R) * (a.N + 1) + (s < R ? hh : tt);
+            const int b = a.row_ptr[row], e = a.row_ptr[row + 1];
+            seg_beg[s] = b;
+            seg_off[s] = off;
+            off += e > b ? e - b : 0;
+        }
+        seg_off[ns] = off;
+    }
+    __syncthreads();
+    const long long base = a.qptr[q];
+    const long long room = a.qptr[q + 1] - base;
+    const int total = (long long)seg_off[ns] < room ? seg_off[ns] : (int)(room > 0 ? room : 0);
+    for (int j = tid; j < total; j += NT) {
+        int s = 0;
+        while (j >= seg_off[s + 1]) ++s;
+        const int pos = seg_beg[s] + (j - seg_off[s]);
+        const f32x4* e4 = (const f32x4*)(a.E + (size_t)a.col[pos] * D);
+        const f32x4* g4 = (const f32x4*)(Gs + s * D);
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < D / 4; ++i) {
+            const f32x4 ev = e4[i], gv = g4[i];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) acc[c] = fmaf(gv[c], ev[c], acc[c]);
+        }
+        a.entry[base + j] = a.eoc ? (int)a.eoc[pos] : pos;
+        a.grad[base + j] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+    }
+}
+
+// ---- selection -------------------------------------------------------------------------------------------------
+constexpr int TK_BUF = 1024;                           // keys sorted per pass
+constexpr int TK_CH = TK_BUF - IDDGCN_TOPK_MAX;        // new candidates per pass; buf[TK_CH..) holds the running top
+
+// larger key = better candidate: value descending (-0.0 taken as +0.0), then id ascending; 0 = no candidate
+__device__ __forceinline__ unsigned long long make_key(float v, int c) {
+    if (v == 0.0f) v = 0.0f;
+    unsigned u = __float_as_uint(v);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)c);
+}
+
+__device__ __forceinline__ float key_value(unsigned long long key) {
+    const unsigned u = (unsigned)(key >> 32);
+    return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
+}
+
+__global__ __launch_bounds__(NT) void topk_kernel(int k, const long long* __restrict__ qptr,
+                                                  const int* __restrict__ entry, const float* __restrict__ grad,
+                                                  int* __restrict__ topk_entry, float* __restrict__ topk_val,
+                                                  int* __restrict__ n_pos) {
+    __shared__ unsigned long long buf[TK_BUF];
+    __shared__ int sel[IDDGCN_TOPK_MAX];
+    __shared__ int cnt[NT / 64];
+    const int tid = threadIdx.x;
+    const int q = blockIdx.x;
+    const long long b0 = qptr[q];
+    const long long len = qptr[q + 1] - b0;
+    const int* ent = entry + b0;
+    const float* val = grad + b0;
+
+    for (int j = tid; j < TK_BUF; j += NT) buf[j] = 0ull;
+    __syncthreads();
+    unsigned long long thr = 0ull;       // the current k-th key
+    int pos = 0;
+    for (long long base = 0; base < len; base += TK_CH) {
+        unsigned long long keys[TK_BUF / NT];
+        int any = 0;
+#pragma unroll
+        for (int u = 0; u < TK_BUF / NT; ++u) {
+            const int j = tid + u * NT;
+            unsigned long long key = 0ull;
+            if (j < TK_CH && base + j < len) {
+                const float v = val[base + j];
+                key = make_key(v, ent[base + j]);
+                pos += v > 0.0f;
+            }
+            keys[u] = key;
+            any |= key > thr;
+        }
+        if (__syncthreads_or(any)) {
+#pragma unroll
+            for (int u = 0; u < TK_BUF / NT; ++u) {
+                const int j = tid + u * NT;
+                if (j < TK_CH) buf[j] = keys[u];
+            }
+            __syncthreads();
+            // bitonic sort, descending
+            for (int k2 = 2; k2 <= TK_BUF; k2 <<= 1)
+                for (int j = k2 >> 1; j > 0; j >>= 1) {
+                    for (int t = tid; t < TK_BUF / 2; t += NT) {
+                        const int x0 = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                        const int x1 = x0 | j;
+                        const unsigned long long x = buf[x0], y = buf[x1];
+                        const bool desc = (x0 & k2) == 0;
+                        if ((x < y) == desc) {
+                            buf[x0] = y;
+                            buf[x1] = x;
+                        }
+                    }
+                    __syncthreads();
+                }
+            const unsigned long long top = tid < IDDGCN_TOPK_MAX ? buf[tid] : 0ull;
+            thr = buf[k - 1];
+            __syncthreads();
+            if (tid < IDDGCN_TOPK_MAX) buf[TK_CH + tid] = top;
+        }
+    }
+    __syncthreads();
+    int zero = 0;
+    if (tid < k) {
+        const unsigned long long key = buf[TK_CH + tid];
+        const int c = key ? (int)(0xFFFFFFFFu - (unsigned)key) : -1;
+        const float v = key ? key_value(key) : -INFINITY;
+        topk_entry[(size_t)q * k + tid] = c;
+        topk_val[(size_t)q * k + tid] = v;
+        sel[tid] = c;
+        zero = c >= 0 && v == 0.0f;
+    }
+    // the keys carry -0.0 as +0.0: a selected zero gets its stored sign back
+    if (__syncthreads_or(zero)) {
+        for (long long j = tid; j < len; j += NT) {
+            const float v = val[j];
+            if (v == 0.0f && (__float_as_uint(v) >> 31)) {
+                const int c = ent[j];
+                for (int i = 0; i < k; ++i)
+                    if (sel[i] == c) topk_val[(size_t)q * k + i] = v;
+            }
+        }
+    }
+    // n_pos: an integer sum (any order gives the same result)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) pos += __shfl_xor(pos, o, 64);
+    if ((tid & 63) == 0) cnt[tid >> 6] = pos;
+    __syncthreads();
+    if (tid == 0) {
+        int n = 0;
+        for (int wv = 0; wv < NT / 64; ++wv) n += cnt[wv];
+        n_pos[q] = n;
+    }
+}
+
+}  // namespace xpl
+
+extern "C" {
+
+int iddgcn_explain_seeds_f32(void* stream, int Q, int N, int d, int R, const int* h, const int* r, const int* t,
+                             float scale, const float* ES1, const float* P, long long p_layer_stride,
+                             long long p_rel_stride, const float* W, const float* Ssm, long long w_layer_stride,
+                             const float* X, long long x_layer_stride, const float* K1, const float* K2,
+                             const float* K3, const float* S2, const float* S3, const float* Wa2, const float* Wa3,
+                             const float* rel, float* G, float* p) {
+    using namespace xpl;
+    if (d != 32 && d != 64) return IDDGCN_E_BAD_DIM;
+    if (R < 1 || R > MAX_R) return IDDGCN_E_BAD_REL;
+    if (Q < 0 || N < 1) return IDDGCN_E_BAD_ARG;
+    if (Q == 0) return 0;
+    if (!h || !r || !t || !ES1 || !P || !W || !Ssm || !X || !K1 || !K2 || !K3 || !S2 || !S3 || !Wa2 || !Wa3 || !rel ||
+        !G || !p)
+        return IDDGCN_E_BAD_ARG;
+    if (p_layer_stride < 0 || p_rel_stride < 0 || w_layer_stride < 0 || x_layer_stride < 0) return IDDGCN_E_BAD_ARG;
+    if (((uintptr_t)ES1 & 15) || ((uintptr_t)P & 15) || ((uintptr_t)G & 15) || (p_layer_stride & 3) ||
+        (p_rel_stride & 3))
+        return IDDGCN_E_BAD_ARG;
+    SeedP a;
+    a.Q = Q; a.N = N; a.R = R;
+    a.h = h; a.r = r; a.t = t;
+    a.scale = scale;
+    a.ES1 = ES1; a.P = P; a.pls = p_layer_stride; a.prs = p_rel_stride;
+    a.W = W; a.Ssm = Ssm; a.wls = w_layer_stride;
+    a.X = X; a.xls = x_layer_stride;
+    a.K[0] = K1; a.K[1] = K2; a.K[2] = K3;
+    a.S[0] = S2; a.S[1] = S3;
+    a.Wa[0] = Wa2; a.Wa[1] = Wa3;
+    a.rel = rel; a.G = G; a.p = p;
+    const unsigned blocks = (unsigned)((Q + QT - 1) / QT);
+    hipStream_t st = (hipStream_t)stream;
+    if (d == 64)
+        hipLaunchKernelGGL(seeds_kernel<64>, dim3(blocks), dim3(NT), 0, st, a);
+    else
+        hipLaunchKernelGGL(seeds_kernel<32>, dim3(blocks), dim3(NT), 0, st, a);
+    return (int)hipGetLastError();
+}
+
+int iddgcn_explain_row_grads_f32(void* stream, int Q, int N, int d, int R, const int* h, const int* t,
+                                 const int* row_ptr, const int* col, const long long* entry_of_csr, const float* G,
+                                 const float* E, const long long* qptr, int* entry, float* grad) {
+    using namespace xpl;
+    if (d != 32 && d != 64) return IDDGCN_E_BAD_DIM;
+    if (R < 1 || R > MAX_R) return IDDGCN_E_BAD_REL;
+    if (Q < 0 || N < 1) return IDDGCN_E_BAD_ARG;
+    if (Q == 0) return 0;
+    if (!h || !t || !row_ptr || !col || !G || !E || !qptr || !entry || !grad) return IDDGCN_E_BAD_ARG;
+    if (((uintptr_t)E & 15) || ((uintptr_t)G & 15)) return IDDGCN_E_BAD_ARG;
+    RowP a;
+    a.N = N; a.R = R;
+    a.h = h; a.t = t; a.row_ptr = row_ptr; a.col = col; a.eoc = entry_of_csr;
+    a.G = G; a.E = E; a.qptr = qptr; a.entry = entry; a.grad = grad;
+    hipStream_t st = (hipStream_t)stream;
+    if (d == 64)
+        hipLaunchKernelGGL(row_grads_kernel<64>, dim3((unsigned)Q), dim3(NT), 0, st, a);
+    else
+        hipLaunchKernelGGL(row_grads_kernel<32>, dim3((unsigned)Q), dim3(NT), 0, st, a);
+    return (int)hipGetLastError();
+}
+
+int iddgcn_explain_topk_f32(void* stream, int Q, int k, const long long* qptr, const int* entry, const float* grad,
+                            int* topk_entry, float* topk_val, int* n_pos) {
+    using namespace xpl;
+    if (Q < 0 || k < 1 || k > IDDGCN_TOPK_MAX) return IDDGCN_E_BAD_ARG;
+    if (Q == 0) return 0;
+    // entry / grad may be null when every segment is empty: they are then never read
+    if (!qptr || !topk_entry || !topk_val || !n_pos) return IDDGCN_E_BAD_ARG;
+    hipLaunchKernelGGL(topk_kernel, dim3((unsigned)Q), dim3(NT), 0, (hipStream_t)stream, k, qptr, entry, grad,
+                       topk_entry, topk_val, n_pos);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -1122,6 +1122,79 @@ class Engine:
         ops.sddmm_csr(adj.fwd_ptr, adj.fwd_col, ws.dAE, params["E"], dv, R, N)
         return adj.to_entry_order(dv), ed.unsort(ws.p)
 
+    def value_grads_batch(self, params, adj, triples, scale=1.0, max_entries=1 << 22):
+        """value_grads for Q single-triple predictions at once, from the rows that matter.
+
+        The prediction of (h, r, t) reads A_r only through AE_r[h] and AE_r[t], so d p / d A_r[i, j] =
+        <dAE_r[i], E[j]> is exactly 0 unless i is h or t: the non-zero part of ``value_grads`` of that one triple is
+        a list of ``deg(h) + deg(t)`` candidates.  The node tables are computed once (``_node_tables``); then per
+        chunk of queries — at most ``max_entries`` candidates, at least one query — two launches: ops.explain_seeds
+        (each query's dAE rows) and ops.explain_row_grads (the ragged SDDMM).  fp32 features with D in {32, 64}; the
+        per-triple ``value_grads`` / ``explain.explaine`` cover every other width and mode.
+
+        ``triples``: (Q, 3) (h, r, t).  Returns a dict of device tensors: ``p`` (Q,) the predictions; ``qptr``
+        (Q + 1,) int64; ``entry`` (qptr[-1],) int32 — query q's candidates are entry[qptr[q]:qptr[q + 1]], entry ids
+        in the caller's entry order, relation after relation, as the concatenation of ``value_grads``' list (rows of
+        h relation by relation, then rows of t when t != h) — and ``grad`` (qptr[-1],), the gradient of
+        ``scale * p_q`` w.r.t. that entry's value.  Every entry not listed has gradient exactly 0."""
+        if self.node_shard is not None or self.spmm_shard is not None or self.row_shard is not None:
+            raise L.IddgcnError("value_grads_batch: not available on an Engine with node_shard / spmm_shard / "
+                                "row_shard set")
+        N, R, D, dev = self.N, self.R, self.D, self.device
+        if D not in (32, 64) or self.features != "f32":
+            raise L.IddgcnError("value_grads_batch takes D in {32, 64} with fp32 features: use value_grads / "
+                                "explain.explaine (the per-triple path) for this engine")
+        q = np.asarray(triples.cpu() if isinstance(triples, torch.Tensor) else triples).astype(np.int64)
+        if q.ndim != 2 or q.shape[1] != 3:
+            raise L.IddgcnError(f"triples must be (Q, 3), got {q.shape}")
+        Q = q.shape[0]
+        if Q and (min(q[:, 0].min(), q[:, 2].min()) < 0 or max(q[:, 0].max(), q[:, 2].max()) >= N):
+            raise L.IddgcnError("triple entity index out of range [0, num_entities)")
+        if Q and (q[:, 1].min() < 0 or q[:, 1].max() >= R):
+            raise L.IddgcnError("triple relation index out of range [0, num_relations)")
+        if int(max_entries) < 1:
+            raise ValueError(f"max_entries must be positive, got {max_entries}")
+        i32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=dev)  # noqa: E731
+        h, r, t = i32(q[:, 0]), i32(q[:, 1]), i32(q[:, 2])
+        self.finish_pending()
+        # candidate counts from the row degrees, prefix-summed on the device
+        ptr = adj.fwd_ptr.view(R, N + 1)
+        deg = (ptr[:, 1:] - ptr[:, :-1]).sum(0, dtype=torch.int64)
+        hl, tl = h.long(), t.long()
+        qptr = torch.zeros(Q + 1, dtype=torch.int64, device=dev)
+        if Q:
+            torch.cumsum(deg[hl] + torch.where(hl != tl, deg[tl], torch.zeros_like(hl)), 0, out=qptr[1:])
+        qp = qptr.cpu().numpy()
+        out = {"p": torch.empty(Q, dtype=torch.float32, device=dev), "qptr": qptr,
+               "entry": torch.empty(int(qp[-1]), dtype=torch.int32, device=dev),
+               "grad": torch.empty(int(qp[-1]), dtype=torch.float32, device=dev)}
+        if Q == 0:
+            return out
+        ws = next((w for (_, tr), w in self._ws.items() if not tr), None) or self.workspace(1, False)
+        with self._mark("xb_node_tables"):
+            self._node_tables(params, adj, ws)
+        K = tuple(params[f"K{l}"] for l in (1, 2, 3))
+        # an identity entry order (DeviceAdjacency.from_triples) needs no map
+        eoc = None if adj.fwd_src is adj.fwd_pos else adj.fwd_src
+        chunks, q0 = [], 0
+        while q0 < Q:
+            q1 = max(q0 + 1, int(np.searchsorted(qp, qp[q0] + int(max_entries), side="right")) - 1)
+            chunks.append((q0, min(q1, Q)))
+            q0 = chunks[-1][1]
+        G = torch.empty(max(b - a for a, b in chunks), 2, R, D, dtype=torch.float32, device=dev)
+        for q0, q1 in chunks:
+            g = G[:q1 - q0]
+            with self._mark("xb_seeds"):
+                ops.explain_seeds(h[q0:q1], r[q0:q1], t[q0:q1], ws.ES1, ws.P, ws.W, ws.Ssm, ws.X, K, params["S2"],
+                                  params["S3"], params["Wa2"], params["Wa3"], params["rel"], scale, g, out["p"][q0:q1])
+            if qp[q1] == qp[q0]:          # no stored entry in any of the chunk's rows
+                continue
+            with self._mark("xb_row_grads"):
+                # the chunk's own qptr slice: its offsets stay absolute, into the full entry / grad arrays
+                ops.explain_row_grads(h[q0:q1], t[q0:q1], adj.fwd_ptr, adj.fwd_col, g, params["E"], qptr[q0:q1 + 1],
+                                      out["entry"], out["grad"], eoc)
+        return out
+
 
 def step_flops(N, R, D, T, M):
     """Algorithmic work of one training step (W_gemm)."""

@@ -23,11 +23,13 @@ one SDDMM (``iddgcn_sddmm_csr_f32``); masked values go to the device CSR with
 TF's seeded ``tf.random.normal`` mask init cannot be replayed without TF: pass ``init_value`` to
 use a specific one (default: numpy N(0,1) with the given seed).
 """
+import time
+
 import numpy as np
 import torch
 
 from . import ops
-from ._lib import IddgcnError
+from ._lib import TOPK_MAX, IddgcnError
 from .graph import DeviceAdjacency, _as_triples, get_adj_mats
 
 
@@ -85,6 +87,87 @@ def explaine(model, adjacency_data, test_triples, top_k=10, graph=True):
             scores.append(s)
         return np.stack(preds), np.stack(scores)
     return _ExplaineGraph(eng, params, dadj, top_k).run(triples)
+
+
+def rank_sparse_gradient(entry, grad, total_nnz, top_k):
+    """get_pred's ranking of a full (total_nnz,) gradient vector that is zero outside its candidate list, without
+    building it (pure numpy).  ``entry`` (distinct ids in [0, total_nnz)) and ``grad`` are one query's candidates;
+    every other entry has gradient 0.  The stable descending order of the full vector is: the positive candidates
+    (descending, ties by ascending id), then the zero class — every non-candidate entry and every candidate that is
+    exactly 0 — by ascending id, then the negative candidates.  Returns (ids [k], scores [k] float32),
+    k = min(top_k, total_nnz); work O(len(entry) + k), not O(total_nnz)."""
+    entry = np.asarray(entry, np.int64)
+    grad = np.asarray(grad, np.float32)
+    if entry.ndim != 1 or entry.shape != grad.shape:
+        raise ValueError(f"entry and grad must be 1-d and of one length, got {entry.shape} and {grad.shape}")
+    k = min(int(top_k), int(total_nnz))
+    by_id = np.argsort(entry, kind="stable")
+    entry, grad = entry[by_id], grad[by_id]
+    pos, neg = grad > 0, grad < 0
+    pe, pg = entry[pos], grad[pos]
+    o = np.argsort(-pg, kind="stable")[:k]                       # ids ascend already: ties keep ascending id
+    ids, sc = [pe[o]], [pg[o]]
+    need = k - len(o)
+    if need > 0:
+        # the first `need` ids of the zero class lie in [0, need + #non-zero candidates)
+        nonzero = entry[pos | neg]
+        zid = np.setdiff1d(np.arange(min(int(total_nnz), need + len(nonzero)), dtype=np.int64), nonzero,
+                           assume_unique=True)[:need]
+        zs = np.zeros(len(zid), np.float32)
+        zc = ~(pos | neg)                                         # zero-valued candidates keep their stored sign
+        if len(zid) and zc.any():
+            ze, zg = entry[zc], grad[zc]
+            at = np.minimum(np.searchsorted(zid, ze), len(zid) - 1)
+            hit = zid[at] == ze
+            zs[at[hit]] = zg[hit]
+        ids.append(zid)
+        sc.append(zs)
+        need -= len(zid)
+    if need > 0:
+        ne, ng = entry[neg], grad[neg]
+        o = np.argsort(-ng, kind="stable")[:need]
+        ids.append(ne[o])
+        sc.append(ng[o])
+    return np.concatenate(ids), np.concatenate(sc).astype(np.float32)
+
+
+def explaine_batched(model, adjacency_data, test_triples, top_k=10, stats=None):
+    """explaine for all test triples in a fixed number of launches (Engine.value_grads_batch + ops.explain_topk):
+    the same return contract, (preds [n, k, 3], scores [n, k]) with k = min(top_k, total nnz), and the ranking of the
+    FULL gradient vector as get_pred gives it.  The gradient of a triple's prediction is zero outside the adjacency
+    rows of its head and tail, so only those candidates are computed; a triple with at least k positive candidates
+    is ranked by the kernel, the others (and every triple when k > 64) are completed on the host from their
+    candidate list (rank_sparse_gradient).  fp32 features with D in {32, 64}: IddgcnError otherwise (use explaine).
+    ``stats``: an optional dict that receives ``host_completed`` (triples finished on the host) and
+    ``host_complete_s`` (the seconds that took), for tools/bench_explain_batched.py."""
+    eng, params = _model_state(model)
+    N, R = model.num_entities, model.num_relations
+    adj_mats = get_adj_mats(adjacency_data, N, R)
+    dadj = DeviceAdjacency(adj_mats, N, eng.device)
+    triples = _as_triples(test_triples)
+    n, total = len(triples), dadj.total_nnz
+    k = min(int(top_k), total)
+    out = eng.value_grads_batch(params, dadj, triples)
+    rel = np.repeat(np.arange(R), dadj.nnz)
+    trip_all = np.stack([np.concatenate(dadj.rows), rel, np.concatenate(dadj.cols)], 1).astype(np.int64)
+    ids = np.zeros((n, k), np.int64)
+    scores = np.zeros((n, k), np.float32)
+    if n == 0 or k == 0:
+        return trip_all[ids], scores
+    kk = min(k, TOPK_MAX)
+    with eng._mark("xb_topk"):
+        te, tv, npos = ops.explain_topk(out["qptr"], out["entry"], out["grad"], kk)
+    npos = npos.cpu().numpy()
+    done = (npos >= k) if kk == k else np.zeros(n, bool)
+    ids[done], scores[done] = te.cpu().numpy()[done], tv.cpu().numpy()[done]
+    t0 = time.perf_counter()
+    if not done.all():
+        qp, entry, grad = out["qptr"].cpu().numpy(), out["entry"].cpu().numpy(), out["grad"].cpu().numpy()
+        for j in np.flatnonzero(~done):
+            ids[j], scores[j] = rank_sparse_gradient(entry[qp[j]:qp[j + 1]], grad[qp[j]:qp[j + 1]], total, k)
+    if stats is not None:
+        stats.update(host_completed=int((~done).sum()), host_complete_s=time.perf_counter() - t0)
+    return trip_all[ids], scores
 
 
 class _SingleEdge:

@@ -804,3 +804,118 @@ def rank_topk(s, target, k, fptr=None, fidx=None, greater=None, equal=None, topk
     L.check(L.lib().iddgcn_rank_topk_f32(_stream(), Q, N, k, _ptr(s), _ptr(target), _ptr(fptr), _ptr(fidx),
                                          _ptr(greater), _ptr(equal), _ptr(topk_idx), _ptr(topk_val)), "rank_topk")
     return greater, equal, topk_idx, topk_val
+
+
+# -- batched explaiNE (include/iddgcn_explain.h) ---------------------------------------------------
+def _layered(t, shape, nm):
+    """A (3, ..) fp32 GPU view whose layers are contiguous blocks of rows (the engine's ws.P / ws.W / ws.X)."""
+    if t is None or not t.is_cuda or t.dtype != _F32:
+        raise L.IddgcnError(f"{nm} must be an fp32 GPU tensor (no CPU fallback)")
+    if tuple(t.shape) != shape or t.stride(-1) != 1 or t.stride(-2) != shape[-1]:
+        raise L.IddgcnError(f"{nm} must be {shape} with contiguous rows")
+
+
+def explain_seeds(h, r, t, ES1, P, W, Ssm, X, K, S2, S3, Wa2, Wa3, rel, scale=1.0, G=None, p=None):
+    """dAE rows of Q predictions (iddgcn_explain_seeds_f32; D in {32, 64}, fp32 tables): for query q = (h[q], r[q],
+    t[q]) the tail chain is recomputed from the node tables and the backward of ``scale * p_q`` gives
+    G[q, 0] = dAE[:, h[q]] and G[q, 1] = dAE[:, t[q]] ((R, D) each, the query's own contributions: at h == t the
+    row's gradient is their sum) and p[q].  P (3, R, N, D), W, Ssm (3, N, R), X (3, N, D): the engine's ws.P / ws.W /
+    ws.Ssm / ws.X; ES1 (N, D); K = (K1, K2, K3), (R, D, D) each; S2, S3 (D, D); Wa2, Wa3 (D, R); rel (R, D).
+    Returns (G (Q, 2, R, D), p (Q,)), allocated when not given."""
+    R, D = rel.shape
+    N = ES1.shape[0]
+    Q = h.shape[0]
+    _idx_ok(h, Q, N, "h")
+    _idx_ok(r, Q, R, "r")
+    _idx_ok(t, Q, N, "t")
+    if len(K) != 3:
+        raise L.IddgcnError("explain_seeds: K must be (K1, K2, K3)")
+    for x, shape, nm in ((ES1, (N, D), "ES1"), (S2, (D, D), "S2"), (S3, (D, D), "S3"), (Wa2, (D, R), "Wa2"),
+                         (Wa3, (D, R), "Wa3"), (rel, (R, D), "rel"), (K[0], (R, D, D), "K1"), (K[1], (R, D, D), "K2"),
+                         (K[2], (R, D, D), "K3")):
+        if x is None:
+            raise L.IddgcnError(f"explain_seeds: {nm} is required")
+        _req(x, _F32, shape, nm)
+    _layered(P, (3, R, N, D), "P")
+    _layered(W, (3, N, R), "W")
+    _layered(Ssm, (3, N, R), "Ssm")
+    _layered(X, (3, N, D), "X")
+    if P.stride(1) < N * D:
+        raise L.IddgcnError("explain_seeds: the relations of P overlap")
+    if W.stride(0) != Ssm.stride(0):
+        raise L.IddgcnError("explain_seeds: W and Ssm must share their layer stride")
+    G = torch.empty(Q, 2, R, D, dtype=_F32, device=ES1.device) if G is None else G
+    p = torch.empty(Q, dtype=_F32, device=ES1.device) if p is None else p
+    _req(G, _F32, (Q, 2, R, D), "G")
+    _req(p, _F32, (Q,), "p")
+    if (ES1.data_ptr() | P.data_ptr() | G.data_ptr()) & 15 or P.stride(0) % 4 or P.stride(1) % 4:
+        raise L.IddgcnError("explain_seeds: ES1 / P / G must be 16-byte aligned, P's layer and relation strides "
+                            "multiples of 4 floats")
+    L.check(L.lib().iddgcn_explain_seeds_f32(
+        _stream(), Q, N, D, R, _ptr(h), _ptr(r), _ptr(t), float(scale), _ptr(ES1), _ptr(P), P.stride(0), P.stride(1),
+        _ptr(W), _ptr(Ssm), W.stride(0), _ptr(X), X.stride(0), _ptr(K[0]), _ptr(K[1]), _ptr(K[2]), _ptr(S2), _ptr(S3),
+        _ptr(Wa2), _ptr(Wa3), _ptr(rel), _ptr(G), _ptr(p)), "explain_seeds")
+    return G, p
+
+
+def explain_row_grads(h, t, row_ptr, col, G, E, qptr, entry, grad, entry_of_csr=None):
+    """The ragged SDDMM of batched explaiNE (iddgcn_explain_row_grads_f32): query q's candidates — the stored entries
+    of row h[q] of every relation, then (h[q] != t[q]) of row t[q] — written at qptr[q] + j: ``entry`` = the CSR
+    position mapped through ``entry_of_csr`` (int64, e.g. DeviceAdjacency.fwd_src; None = the position), ``grad`` =
+    <G[q, side, rel], E[col]>.  row_ptr (R (N + 1)), col: the batched forward CSR; qptr (Q + 1) int64 with
+    qptr[q + 1] - qptr[q] the sum of the query's row degrees; entry int32 / grad fp32 of at least qptr[-1] elements."""
+    Q, two, R, D = G.shape
+    N = E.shape[0]
+    _req(G, _F32, (Q, 2, R, D), "G")
+    _req(E, _F32, (N, D), "E")
+    _idx_ok(h, Q, N, "h")
+    _idx_ok(t, Q, N, "t")
+    _req(row_ptr, _I32, (R * (N + 1),), "row_ptr")
+    _req(col, _I32, None, "col")
+    _req(qptr, torch.int64, (Q + 1,), "qptr")
+    _req(entry, _I32, None, "entry")
+    _req(grad, _F32, None, "grad")
+    if entry.dim() != 1 or grad.shape != entry.shape:
+        raise L.IddgcnError("explain_row_grads: entry and grad must be 1-d and of one length")
+    if entry_of_csr is not None:
+        _req(entry_of_csr, torch.int64, (col.shape[0],), "entry_of_csr")
+    if (E.data_ptr() | G.data_ptr()) & 15:
+        raise L.IddgcnError("explain_row_grads: E / G must be 16-byte aligned")
+    if CHECK_INDEX_RANGES and Q:
+        qp = qptr.cpu()
+        if int(qp[0]) < 0 or bool((qp[1:] < qp[:-1]).any()) or int(qp[-1]) > entry.numel():
+            raise L.IddgcnError("explain_row_grads: qptr must ascend within [0, len(entry)]")
+    L.check(L.lib().iddgcn_explain_row_grads_f32(
+        _stream(), Q, N, D, R, _ptr(h), _ptr(t), _ptr(row_ptr), _ptr(col), _ptr(entry_of_csr), _ptr(G), _ptr(E),
+        _ptr(qptr), _ptr(entry), _ptr(grad)), "explain_row_grads")
+
+
+def explain_topk(qptr, entry, grad, k, topk_entry=None, topk_val=None, n_pos=None):
+    """Per query the k best of its candidate segment [qptr[q], qptr[q + 1]) (iddgcn_explain_topk_f32): descending by
+    value, ties by ascending entry id, padded with -1 / -inf; n_pos[q] = its candidates with value > 0.
+    Returns (topk_entry (Q, k) int32, topk_val (Q, k), n_pos (Q,) int32), allocated when not given."""
+    k = int(k)
+    if not 1 <= k <= L.TOPK_MAX:
+        raise L.IddgcnError(f"explain_topk: k must be in [1, {L.TOPK_MAX}]")
+    _req(qptr, torch.int64, None, "qptr")
+    if qptr.dim() != 1 or qptr.shape[0] < 1:
+        raise L.IddgcnError("explain_topk: qptr must be (Q + 1,)")
+    Q = qptr.shape[0] - 1
+    _req(entry, _I32, None, "entry")
+    _req(grad, _F32, None, "grad")
+    if entry.dim() != 1 or grad.shape != entry.shape:
+        raise L.IddgcnError("explain_topk: entry and grad must be 1-d and of one length")
+    if CHECK_INDEX_RANGES and Q:
+        qp = qptr.cpu()
+        if int(qp[0]) < 0 or bool((qp[1:] < qp[:-1]).any()) or int(qp[-1]) > entry.numel():
+            raise L.IddgcnError("explain_topk: qptr must ascend within [0, len(entry)]")
+    dev = qptr.device
+    topk_entry = torch.empty(Q, k, dtype=_I32, device=dev) if topk_entry is None else topk_entry
+    topk_val = torch.empty(Q, k, dtype=_F32, device=dev) if topk_val is None else topk_val
+    n_pos = torch.empty(Q, dtype=_I32, device=dev) if n_pos is None else n_pos
+    _req(topk_entry, _I32, (Q, k), "topk_entry")
+    _req(topk_val, _F32, (Q, k), "topk_val")
+    _req(n_pos, _I32, (Q,), "n_pos")
+    L.check(L.lib().iddgcn_explain_topk_f32(_stream(), Q, k, _ptr(qptr), _ptr(entry), _ptr(grad), _ptr(topk_entry),
+                                            _ptr(topk_val), _ptr(n_pos)), "explain_topk")
+    return topk_entry, topk_val, n_pos
