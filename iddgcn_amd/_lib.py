@@ -52,6 +52,20 @@ class TnArgs(ctypes.Structure):
     _fields_ = [("M", cll), ("A", vp), ("B", vp), ("C", vp), ("accumulate", ci)]
 
 
+class MaskExplainArgs(ctypes.Structure):
+    """Mirror of iddgcn_mask_explain_t (include/iddgcn_explain.h)."""
+    _fields_ = [
+        ("N", ci), ("d", ci), ("R", ci), ("num_epochs", ci), ("epochs_base", ci), ("n_queries", ci),
+        ("qids", vp), ("h", vp), ("r", vp), ("t", vp), ("qptr", vp),
+        ("entry", vp), ("crel", vp), ("ccol", vp), ("crole", vp),
+        ("E", vp), ("K", vp * 3), ("KT", vp * 3), ("S", vp * 3), ("ST", vp * 3), ("Wa", vp * 3), ("ba", vp * 3),
+        ("rel", vp),
+        ("init_e", vp), ("m", vp), ("v", vp), ("steps", vp), ("alpha", vp),
+        ("b1", cf), ("b2", cf), ("eps", cf),
+        ("target_ratios", vp), ("out", vp),
+    ]
+
+
 TN_BATCH = 4
 SCREEN_TAIL, SCREEN_HEAD = 0, 1                   # include/iddgcn_screen.h IDDGCN_SCREEN_*
 TOPK_MAX = 64
@@ -126,6 +140,8 @@ SIGNATURES = {
                                       vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "iddgcn_explain_row_grads_f32": (ci, [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "iddgcn_explain_topk_f32": (ci, [vp, ci, ci, vp, vp, vp, vp, vp, vp]),
+    # batched mask explainers (added symbol only)
+    "iddgcn_mask_explain_f32": (ci, [vp, ctypes.POINTER(MaskExplainArgs)]),
 }
 
 _lib = None

@@ -1,4 +1,4 @@
-// explain.hip — batched explaiNE for gfx950 (include/iddgcn_explain.h).
+// explain.hip — batched explaiNE and the batched mask explainers for gfx950 (include/iddgcn_explain.h).
 //
 // The prediction of (h, r, t) reads A_r only through AE_r[h] and AE_r[t], so its gradient w.r.t. the adjacency values
 // lives in rows h and t alone.  Three kernels, none of them proportional to N or nnz:
@@ -15,6 +15,8 @@
 //
 // topk_kernel: one workgroup per query over its candidate segment: rank_topk_kernel's passes (screen.hip), a bitonic
 // sort of 64-bit (value, entry id) keys in LDS merged into the running top 64.
+//
+// mask_explain_kernel (further down): every epoch of one triple's mask training in one workgroup.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -430,6 +432,339 @@ __global__ __launch_bounds__(NT) void topk_kernel(int k, const long long* __rest
     }
 }
 
+// ---- batched mask explainers -----------------------------------------------------------------------------------
+// mask_explain_kernel: one workgroup per query runs the unmasked forward and every epoch of the query's mask training
+// (iddgcn_explain.h) on chip.  Per-candidate state (mask in a.out, m, v) stays in global memory, each candidate owned by
+// one thread (j = tid mod NT) for the whole kernel; the masked values are staged CH at a time for the AE rows, the E
+// rows of the first ES_ROWS candidates once for all epochs (the others are read from global memory every epoch).  Every
+// matrix is read from global memory with lanes along a row (coalesced): K and S in the forward, their transposes in the
+// backward; the small reductions (softmax logits, DistMult, dw) are butterflies over the D lanes of a group.  Four
+// fmaf chains per mat-vec element, (c0 + c1) + (c2 + c3).
+constexpr int CH = 512;            // candidates staged per pass (a multiple of NT: a candidate keeps its thread)
+constexpr int ES_BYTES = 112 * 1024;   // E rows kept in LDS: 448 candidates at d = 64, 896 at d = 32
+
+__device__ __forceinline__ float sigmoid_ref(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// sum over the D lanes of a group (D <= 64 lanes of one wave, all active), a fixed butterfly
+template <int D>
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+    for (int o = D / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// column k of (vh, vt) · M and of v · M: Mk = M + k, M (D, D) row-major in global memory, vectors in LDS.  The loads go
+// out 32 at a time before their fmaf chains (left to itself the scheduler waits for every load in turn).
+template <int D>
+__device__ __forceinline__ void matvec2(const float* __restrict__ Mk, const float* vh, const float* vt, float& yh,
+                                        float& yt) {
+    float ch[4] = {0.f, 0.f, 0.f, 0.f}, ct[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i0 = 0; i0 < D; i0 += 32) {
+        float kv[32];
+#pragma unroll
+        for (int u = 0; u < 32; ++u) kv[u] = Mk[(size_t)(i0 + u) * D];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < 32; ++u) {
+            ch[(u >> 3) & 3] = fmaf(vh[i0 + u], kv[u], ch[(u >> 3) & 3]);
+            ct[(u >> 3) & 3] = fmaf(vt[i0 + u], kv[u], ct[(u >> 3) & 3]);
+        }
+    }
+    yh = (ch[0] + ch[1]) + (ch[2] + ch[3]);
+    yt = (ct[0] + ct[1]) + (ct[2] + ct[3]);
+}
+
+template <int D>
+__device__ __forceinline__ float matvec1(const float* __restrict__ Mk, const float* v) {
+    float c4[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i0 = 0; i0 < D; i0 += 32) {
+        float kv[32];
+#pragma unroll
+        for (int u = 0; u < 32; ++u) kv[u] = Mk[(size_t)(i0 + u) * D];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < 32; ++u) c4[(u >> 3) & 3] = fmaf(v[i0 + u], kv[u], c4[(u >> 3) & 3]);
+    }
+    return (c4[0] + c4[1]) + (c4[2] + c4[3]);
+}
+
+template <int D>
+__global__ __launch_bounds__(NT) void mask_explain_kernel(const iddgcn_mask_explain_t a) {
+    constexpr int GR = NT / D;                 // groups of D lanes: 4 / 8
+    constexpr int RPG = MAX_R / GR;            // relations per group in the AE and mat-vec passes: 2 / 1
+    constexpr int ES_ROWS = ES_BYTES / (4 * D);
+    __shared__ float es[ES_ROWS * D];
+    __shared__ float AE[2][MAX_R][D];
+    __shared__ float P[3][2][MAX_R][D];
+    __shared__ __attribute__((aligned(16))) float G[2][MAX_R][D];
+    __shared__ float x[4][2][D];
+    __shared__ float dx[2][D];
+    __shared__ float dz[2][D];
+    __shared__ float w[3][MAX_R];
+    __shared__ float sm[3][MAX_R];
+    __shared__ float zs[MAX_R];
+    __shared__ float da[MAX_R];
+    __shared__ float du[MAX_R];
+    __shared__ float cnt[MAX_R];
+    __shared__ float gsr[MAX_R];
+    __shared__ float smv[CH];                  // the masked values of a pass, and as multipliers of the two AE rows
+    __shared__ float smvh[CH];
+    __shared__ float smvt[CH];
+    __shared__ int scol[CH];
+    __shared__ int rstart[MAX_R + 1];
+    __shared__ float sc[3];                    // before, -before / (p + 1e-5), p (1 - p)
+
+    const int tid = threadIdx.x;
+    const int R = a.R;
+    const int q = a.qids[blockIdx.x];
+    const int hh = a.h[q], rr = a.r[q], tt = a.t[q];
+    const long long c0 = a.qptr[q];
+    const int n = (int)(a.qptr[q + 1] - c0);
+    const int step0 = a.epochs_base + q * a.num_epochs;
+    const int* ent = a.entry + c0;
+    const int* crel = a.crel + c0;
+    const int* ccol = a.ccol + c0;
+    const int* crole = a.crole + c0;
+    float* mk = a.out + c0;
+    const int k = tid % D, grp = tid / D;
+    const int side2 = (tid / D) & 1;           // the (side, column) a thread owns in the 2 D wide passes
+
+    // load: lazily decayed moments, the mask at its init value, the relation segments of the candidate list
+    if (tid <= MAX_R) rstart[tid] = n;
+    __syncthreads();
+    for (int j = tid; j < n; j += NT) {
+        const int e = ent[j];
+        const int gap = step0 - a.steps[e];
+        if (gap > 0) {
+            a.m[e] *= powf(a.b1, (float)gap);
+            a.v[e] *= powf(a.b2, (float)gap);
+        }
+        mk[j] = a.init_e[e];
+        const int r1 = crel[j];
+        const int r0 = j ? crel[j - 1] : -1;
+        for (int r = r0 + 1; r <= r1; ++r) rstart[r] = j;
+    }
+    if (tid < 2 * D) x[0][side2][k] = a.E[(size_t)(side2 ? tt : hh) * D + k];
+    {
+        const int ns = n < ES_ROWS ? n : ES_ROWS;
+        for (int idx = tid; idx < ns * D; idx += NT) es[idx] = a.E[(size_t)ccol[idx / D] * D + idx % D];
+    }
+    __syncthreads();
+
+    for (int ep = -1; ep < a.num_epochs; ++ep) {
+        // AE rows of h and t (and the relation sums of the masked values), candidates ascending
+        {
+            // group grp owns relations grp, grp + GR; a candidate that feeds neither row (or one only) enters with a
+            // zero multiplier: fmaf(0, e, acc) is acc
+            float ah[RPG], at[RPG], cacc[RPG];
+#pragma unroll
+            for (int ri = 0; ri < RPG; ++ri) ah[ri] = at[ri] = cacc[ri] = 0.f;
+            for (int cb = 0; cb == 0 || cb < n; cb += CH) {
+                const int ce = cb + CH < n ? cb + CH : n;
+                for (int j = cb + tid; j < ce; j += NT) {
+                    const float mv = ep < 0 ? 1.0f : sigmoid_ref(mk[j]);
+                    const int role = crole[j];
+                    smv[j - cb] = mv;
+                    smvh[j - cb] = (role & 1) ? mv : 0.f;
+                    smvt[j - cb] = (role & 2) ? mv : 0.f;
+                    scol[j - cb] = ccol[j];
+                }
+                __syncthreads();
+#pragma unroll
+                for (int ri = 0; ri < RPG; ++ri) {
+                    const int r = grp + ri * GR;
+                    if (r < R) {
+                        const int j0 = rstart[r] > cb ? rstart[r] : cb;
+                        const int j1 = rstart[r + 1] < ce ? rstart[r + 1] : ce;
+                        const int jl = j0 > ES_ROWS ? j0 : ES_ROWS;
+                        const int jm = jl < j1 ? jl : j1;             // [j0, jm): E rows in LDS, [jm, j1): global
+#pragma unroll 4
+                        for (int j = j0; j < jm; ++j) {
+                            const float ev = es[j * D + k];
+                            ah[ri] = fmaf(smvh[j - cb], ev, ah[ri]);
+                            at[ri] = fmaf(smvt[j - cb], ev, at[ri]);
+                            cacc[ri] += smv[j - cb];
+                        }
+                        for (int j = jm; j < j1; ++j) {
+                            const float mh = smvh[j - cb], mt = smvt[j - cb];
+                            if (mh != 0.f || mt != 0.f) {
+                                const float ev = a.E[(size_t)scol[j - cb] * D + k];
+                                ah[ri] = fmaf(mh, ev, ah[ri]);
+                                at[ri] = fmaf(mt, ev, at[ri]);
+                            }
+                            cacc[ri] += smv[j - cb];
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+#pragma unroll
+            for (int ri = 0; ri < RPG; ++ri) {
+                const int r = grp + ri * GR;
+                if (r < R) {
+                    AE[0][r][k] = ah[ri];
+                    AE[1][r][k] = at[ri];
+                    if (k == 0) cnt[r] = cacc[ri];
+                }
+            }
+        }
+        __syncthreads();
+
+        // forward: the reference layer on the two rows
+        for (int l = 0; l < 3; ++l) {
+            for (int r = grp; r < R; r += GR) {
+                const float z = group_sum<D>(x[l][0][k] * a.Wa[l][(size_t)k * R + r]);
+                if (k == 0) zs[r] = z + a.ba[l][r];
+                float ph, pt;
+                matvec2<D>(a.K[l] + (size_t)r * D * D + k, AE[0][r], AE[1][r], ph, pt);
+                P[l][0][r][k] = ph;
+                P[l][1][r][k] = pt;
+            }
+            __syncthreads();
+            if (tid < R) {
+                float mx = -INFINITY;
+                for (int i = 0; i < R; ++i) mx = fmaxf(mx, zs[i]);
+                float sum = 0.f;
+                for (int i = 0; i < R; ++i) sum += expf(zs[i] - mx);
+                const float s = expf(zs[tid] - mx) / sum;
+                sm[l][tid] = s;
+                w[l][tid] = sigmoid_ref(s);
+            }
+            __syncthreads();
+            if (tid < 2 * D) {
+                float v = matvec1<D>(a.S[l] + k, x[l][side2]);
+                for (int r = 0; r < R; ++r) v = fmaf(w[l][r], P[l][side2][r][k], v);
+                x[l + 1][side2][k] = sigmoid_ref(v);
+            }
+            __syncthreads();
+        }
+        float s_dm = 0.f;
+        if (tid < D) s_dm = group_sum<D>(x[3][0][k] * a.rel[(size_t)rr * D + k] * x[3][1][k]);
+        if (tid == 0) {
+            const float p = sigmoid_ref(s_dm);
+            if (ep < 0) sc[0] = p;
+            sc[1] = -sc[0] / (p + 1e-5f);
+            sc[2] = p * (1.0f - p);
+            // the relation-ratio loss: its gradient w.r.t. the masked values of relation r
+            if (a.target_ratios && ep >= 0) {
+                float C = 0.f, dot = 0.f, dr[MAX_R];
+#pragma unroll
+                for (int r = 0; r < MAX_R; ++r)
+                    if (r < R) C += cnt[r];
+#pragma unroll
+                for (int r = 0; r < MAX_R; ++r)
+                    if (r < R) {
+                        const float ratio = cnt[r] / C;
+                        dr[r] = 2.0f * (ratio - a.target_ratios[r]) / (float)R;
+                        dot = fmaf(dr[r], ratio, dot);
+                    }
+#pragma unroll
+                for (int r = 0; r < MAX_R; ++r)
+                    if (r < R) gsr[r] = (dr[r] - dot) / C;
+            }
+        }
+        __syncthreads();
+        if (ep < 0) continue;
+
+        // backward of p: GH, GT
+        if (tid < 2 * D) dx[side2][k] = sc[2] * a.rel[(size_t)rr * D + k] * x[3][1 - side2][k];
+        float Gh[RPG], Gt[RPG];
+#pragma unroll
+        for (int ri = 0; ri < RPG; ++ri) Gh[ri] = Gt[ri] = 0.f;
+        __syncthreads();
+        for (int l = 2; l >= 0; --l) {
+            if (tid < 2 * D) {
+                const float xv = x[l + 1][side2][k];
+                dz[side2][k] = dx[side2][k] * (xv * (1.0f - xv));
+            }
+            __syncthreads();
+            // G_r += w_lr (dz K^l_r^T), from the transposed K: group grp owns relations grp, grp + GR; and the dynamic
+            // weights' dw_r = <dzh, P^l_r[h]> + <dzt, P^l_r[t]>, through the sigmoid
+#pragma unroll
+            for (int ri = 0; ri < RPG; ++ri) {
+                const int r = grp + ri * GR;
+                if (r < R) {
+                    float gh, gt;
+                    matvec2<D>(a.KT[l] + (size_t)r * D * D + k, dz[0], dz[1], gh, gt);
+                    const float wv = w[l][r];
+                    Gh[ri] = fmaf(wv, gh, Gh[ri]);
+                    Gt[ri] = fmaf(wv, gt, Gt[ri]);
+                    if (l > 0) {
+                        const float dw = group_sum<D>(fmaf(dz[0][k], P[l][0][r][k], dz[1][k] * P[l][1][r][k]));
+                        if (k == 0) da[r] = dw * (wv * (1.0f - wv));
+                    }
+                }
+            }
+            if (l == 0) break;
+            __syncthreads();
+            // through the softmax
+            if (tid < R) {
+                float sum = 0.f;
+                for (int i = 0; i < R; ++i) sum = fmaf(sm[l][i], da[i], sum);
+                du[tid] = sm[l][tid] * (da[tid] - sum);
+            }
+            __syncthreads();
+            // dx^{l-1} = dz S^l^T (+ du Walpha^l^T on the head side), from the transposed S
+            if (tid < 2 * D) {
+                float acc = matvec1<D>(a.ST[l] + k, dz[side2]);
+                if (side2 == 0) {
+                    const float* wa = a.Wa[l] + (size_t)k * R;
+                    for (int r = 0; r < R; ++r) acc = fmaf(du[r], wa[r], acc);
+                }
+                dx[side2][k] = acc;
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int ri = 0; ri < RPG; ++ri)
+            if (grp + ri * GR < R) {
+                G[0][grp + ri * GR][k] = Gh[ri];
+                G[1][grp + ri * GR][k] = Gt[ri];
+            }
+        __syncthreads();
+
+        // per candidate: the gradient w.r.t. its mask, one dense-form Adam step
+        const float factor = sc[1];
+        const float alpha = a.alpha[step0 + ep];
+        for (int j = tid; j < n; j += NT) {
+            const int role = crole[j], rl = crel[j], e = ent[j];
+            const f32x4* e4 = (const f32x4*)(a.E + (size_t)ccol[j] * D);
+            float dot = 0.f;
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+                if (role & (1 << s)) {
+                    const f32x4* g4 = (const f32x4*)G[s][rl];
+                    f32x4 c4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int i = 0; i < D / 4; ++i) {
+                        const f32x4 ev = e4[i], gv = g4[i];
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) c4[c] = fmaf(gv[c], ev[c], c4[c]);
+                    }
+                    dot += (c4[0] + c4[1]) + (c4[2] + c4[3]);
+                }
+            float g = dot * factor;
+            if (a.target_ratios) g = (g + gsr[rl]) * 0.5f;
+            const float mkj = mk[j];
+            const float mv = sigmoid_ref(mkj);
+            g = g * mv * (1.0f - mv);
+            float mi = a.m[e], vi = a.v[e];
+            mi = mi + (g - mi) * (1.0f - a.b1);
+            vi = vi + (g * g - vi) * (1.0f - a.b2);
+            a.m[e] = mi;
+            a.v[e] = vi;
+            mk[j] = mkj - (mi * alpha) / (sqrtf(vi) + a.eps);
+        }
+    }
+
+    for (int j = tid; j < n; j += NT) {
+        mk[j] = sigmoid_ref(mk[j]);
+        a.steps[ent[j]] = step0 + a.num_epochs;
+    }
+}
+
 }  // namespace xpl
 
 extern "C" {
@@ -503,6 +838,29 @@ int iddgcn_explain_topk_f32(void* stream, int Q, int k, const long long* qptr, c
     if (!qptr || !topk_entry || !topk_val || !n_pos) return IDDGCN_E_BAD_ARG;
     hipLaunchKernelGGL(topk_kernel, dim3((unsigned)Q), dim3(NT), 0, (hipStream_t)stream, k, qptr, entry, grad,
                        topk_entry, topk_val, n_pos);
+    return (int)hipGetLastError();
+}
+
+int iddgcn_mask_explain_f32(void* stream, const iddgcn_mask_explain_t* args) {
+    using namespace xpl;
+    if (!args) return IDDGCN_E_BAD_ARG;
+    const iddgcn_mask_explain_t& a = *args;
+    if (a.d != 32 && a.d != 64) return IDDGCN_E_BAD_DIM;
+    if (a.R < 1 || a.R > MAX_R) return IDDGCN_E_BAD_REL;
+    if (a.n_queries < 0 || a.N < 1 || a.num_epochs < 0 || a.epochs_base < 0) return IDDGCN_E_BAD_ARG;
+    if (a.n_queries == 0) return 0;
+    if (!a.qids || !a.h || !a.r || !a.t || !a.qptr || !a.E || !a.rel || !a.init_e || !a.m || !a.v || !a.steps ||
+        !a.alpha || !a.out)
+        return IDDGCN_E_BAD_ARG;
+    // the candidate arrays may be null when every segment is empty: they are then never read
+    for (int l = 0; l < 3; ++l)
+        if (!a.K[l] || !a.KT[l] || !a.S[l] || !a.ST[l] || !a.Wa[l] || !a.ba[l]) return IDDGCN_E_BAD_ARG;
+    if ((uintptr_t)a.E & 15) return IDDGCN_E_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (a.d == 64)
+        hipLaunchKernelGGL(mask_explain_kernel<64>, dim3((unsigned)a.n_queries), dim3(NT), 0, st, a);
+    else
+        hipLaunchKernelGGL(mask_explain_kernel<32>, dim3((unsigned)a.n_queries), dim3(NT), 0, st, a);
     return (int)hipGetLastError();
 }
 

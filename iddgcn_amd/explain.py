@@ -22,6 +22,10 @@ one SDDMM (``iddgcn_sddmm_csr_f32``); masked values go to the device CSR with
 * ranking is stable descending (Python ``sorted(..., reverse=True)`` in get_pred).
 TF's seeded ``tf.random.normal`` mask init cannot be replayed without TF: pass ``init_value`` to
 use a specific one (default: numpy N(0,1) with the given seed).
+
+``mask_explainer_batched`` (``gnn_explainer_batched`` / ``iddgcn_explainer_batched``) runs the same mask training from
+each triple's candidate entries alone, every epoch of a triple in one workgroup, with the shared Adam kept as sparse
+per-entry state (see the section below).
 """
 import time
 
@@ -356,6 +360,240 @@ def iddgcn_explainer(model, adjacency_data, test_triples, num_epochs=10, learnin
         raise IddgcnError("target_ratios needs one entry per relation")
     return mask_explainer(model, adjacency_data, test_triples, num_epochs=num_epochs, learning_rate=learning_rate,
                           threshold=threshold, target_ratios=target_ratios, **kw)
+
+
+# -- batched mask explainers ---------------------------------------------------------------------
+# The computation graph of (h, r, t) is every stored entry whose row or column is h or t: its rows h and t are the
+# full graph's rows h and t, and the prediction reads A_r only through AE_r[h] and AE_r[t].  So one epoch of mask
+# training needs the triple's candidate entries, their E rows and a few dozen D x D mat-vecs: every epoch of a triple
+# runs in one workgroup (ops.mask_explain).  The reference's one shared Adam is kept exactly with sparse state: m, v
+# and a "steps applied" count per stored entry of the FULL graph, the moments decayed lazily over the steps an entry
+# sat out (the dense optimizer decays them with zero gradients; what it does to masks outside the current
+# computation graph is never read, the masks being reset after every triple).  Triples that share an entry run in
+# input order, in successive launches (mask_schedule).
+ROLE_HEAD, ROLE_TAIL = 1, 2      # candidate role bits: the entry's row is h / is t (0: only its column is h or t)
+
+
+def _entry_table(dadj):
+    """(row, col, rel, real) of every stored entry of ``dadj`` in entry order (host); real = not the (0,0) = 0
+    placeholder of an empty relation."""
+    row, col = np.concatenate(dadj.rows), np.concatenate(dadj.cols)
+    rel = np.repeat(np.arange(dadj.num_relations, dtype=np.int64), dadj.nnz)
+    real = dadj.base_values.cpu().numpy() != 0
+    return row, col, rel, real
+
+
+def mask_candidates(dadj, triples):
+    """The computation graphs of Q triples as candidate lists over the full adjacency ``dadj`` (a DeviceAdjacency of
+    get_adj_mats(adjacency_data), host entry order: relation-major, row-major sorted).  A triple's candidates are the
+    distinct stored entries with row in {h, t} or column in {h, t}, in ascending entry id — restricted to the triple
+    that is get_adj_mats(get_computation_graph(..))'s order within every relation; the (0,0) = 0 placeholders are no
+    candidates (their value and gradient are exactly 0).  Returns (qptr int64 [Q + 1], entry int32, rel int32, col
+    int32, role int32): role has ROLE_HEAD set when the entry's row is h (it feeds AE[h]) and ROLE_TAIL when it is t."""
+    tr = _as_triples(triples)
+    N = dadj.num_entities
+    if tr.size and (tr[:, [0, 2]].min() < 0 or tr[:, [0, 2]].max() >= N):
+        raise IddgcnError("triple entity index out of range [0, num_entities)")
+    row, col, rel, real = _entry_table(dadj)
+    ids = np.flatnonzero(real)
+    by_row = ids[np.argsort(row[ids], kind="stable")]
+    rptr = np.searchsorted(row[by_row], np.arange(N + 1))
+    by_col = ids[np.argsort(col[ids], kind="stable")]
+    cptr = np.searchsorted(col[by_col], np.arange(N + 1))
+    segs, roles = [], []
+    for h, _, t in tr:
+        nodes = (h,) if h == t else (h, t)
+        e = np.unique(np.concatenate([by_row[rptr[n]:rptr[n + 1]] for n in nodes] +
+                                     [by_col[cptr[n]:cptr[n + 1]] for n in nodes]))
+        segs.append(e)
+        roles.append((row[e] == h) * ROLE_HEAD | (row[e] == t) * ROLE_TAIL)
+    qptr = np.concatenate([[0], np.cumsum([len(e) for e in segs])]).astype(np.int64)
+    entry = np.concatenate(segs).astype(np.int64) if segs else np.zeros(0, np.int64)
+    role = np.concatenate(roles) if roles else np.zeros(0, np.int64)
+    i32 = np.int32
+    return qptr, entry.astype(i32), rel[entry].astype(i32), col[entry].astype(i32), role.astype(i32)
+
+
+def mask_schedule(qptr, entry, total_nnz, schedule="levels"):
+    """The launch level (1-based) of every triple.  The shared optimizer state makes triples whose computation graphs
+    share an entry run in input order: greedily, a triple's level is 1 + the highest level of any earlier triple that
+    touched one of its entries (1 when there is none).  ``schedule="sequential"``: one triple per level."""
+    Q = len(qptr) - 1
+    if schedule == "sequential":
+        return np.arange(1, Q + 1, dtype=np.int64)
+    if schedule != "levels":
+        raise ValueError(f"schedule must be 'levels' or 'sequential', got {schedule!r}")
+    last = np.zeros(int(total_nnz), np.int64)
+    levels = np.zeros(Q, np.int64)
+    for q in range(Q):
+        e = entry[qptr[q]:qptr[q + 1]]
+        levels[q] = 1 + (last[e].max() if len(e) else 0)
+        last[e] = levels[q]
+    return levels
+
+
+def mask_adam_alphas(learning_rate, beta_1, beta_2, first, count):
+    """MaskAdam.apply's fp32 step size of iterations first .. first + count - 1."""
+    f = np.float32
+    t = np.arange(first, first + count).astype(f)
+    return (f(learning_rate) * np.sqrt(f(1) - f(beta_2) ** t) / (f(1) - f(beta_1) ** t)).astype(f)
+
+
+def select_candidates(entry, rel, values, row, col, num_relations, threshold, top_k):
+    """_select on one triple's candidate list (host): values > threshold, relation by relation (a relation whose kept
+    (row, col) indices sum to 0 — nothing kept, or only (0, 0) — is skipped), stable descending, top_k.
+    ``row`` / ``col``: the full adjacency's entry table.  Returns ([k, 3] int64 triples, [k] float32 scores)."""
+    values = np.asarray(values, np.float32)
+    keep = values > threshold
+    for r in range(num_relations):
+        sel = keep & (rel == r)
+        if sel.any() and row[entry[sel]].sum() + col[entry[sel]].sum() == 0:
+            keep = keep & ~sel
+    e, sc = entry[keep].astype(np.int64), values[keep]
+    order = np.argsort(-sc, kind="stable")[:top_k]
+    e = e[order]
+    return np.stack([row[e], rel[keep][order].astype(np.int64), col[e]], 1).reshape(-1, 3), sc[order]
+
+
+def masks_layout(rel, values, num_relations):
+    """One triple's final masked values in mask_explainer's return_masks layout: per relation in computation-graph
+    entry order, a single 0.0 (the placeholder) for a relation that is empty in the computation graph."""
+    values = np.asarray(values, np.float32)
+    return np.concatenate([values[rel == r] if (rel == r).any() else np.zeros(1, np.float32)
+                           for r in range(num_relations)])
+
+
+def mask_explainer_batched(model, adjacency_data, test_triples, *, num_epochs=5, learning_rate=1e-3, threshold=0.2,
+                           init_value=None, seed=123, target_ratios=None, top_k=10, optimizer=None,
+                           return_masks=False, schedule="levels", stats=None):
+    """mask_explainer with every epoch of a triple in one workgroup and one launch per schedule level
+    (ops.mask_explain): the same return contract and the same shared-optimizer semantics.  A ``MaskAdam`` passed in
+    seeds the per-entry state from its dense m / v and offsets the step count by its ``iterations``; on return it holds
+    what the per-triple path would have left, so the two paths continue each other.  fp32 features, D in {32, 64},
+    1 <= R <= 8, unsharded engine: IddgcnError otherwise (use the per-triple mask_explainer).  With ``target_ratios``
+    a triple with no candidate makes the reference divide 0 by 0: IddgcnError up front; without, it returns empty
+    lists.  ``stats``: an optional dict that receives ``levels``, ``candidates`` and ``launch_events`` (a pair of
+    recorded device events around the launches), for tools/bench_explain_masks.py."""
+    eng, params = _model_state(model)
+    N, R = model.num_entities, model.num_relations
+    dev = eng.device
+    if eng.node_shard is not None or eng.spmm_shard is not None or eng.row_shard is not None:
+        raise IddgcnError("mask_explainer_batched: not available on a sharded engine: use the per-triple "
+                          "mask_explainer")
+    if eng.D not in (32, 64) or eng.features != "f32" or not 1 <= R <= 8:
+        raise IddgcnError("mask_explainer_batched takes D in {32, 64}, fp32 features and 1 <= R <= 8: use the "
+                          "per-triple mask_explainer for this model")
+    if target_ratios is not None and len(target_ratios) != R:
+        raise IddgcnError("target_ratios needs one entry per relation")
+    triples = _as_triples(test_triples)
+    Q = len(triples)
+    if Q and (triples[:, 1].min() < 0 or triples[:, 1].max() >= R):
+        raise IddgcnError("triple relation index out of range [0, num_relations)")
+    if init_value is None:
+        init_value = np.random.default_rng(seed).standard_normal((N, N)).astype(np.float32)
+    init = np.asarray(init_value, np.float32).reshape(N, N)
+    dadj = DeviceAdjacency(get_adj_mats(adjacency_data, N, R), N, dev)
+    total = dadj.total_nnz
+    qptr, entry, crel, ccol, crole = mask_candidates(dadj, triples)
+    if target_ratios is not None and Q and (np.diff(qptr) == 0).any():
+        bad = triples[np.flatnonzero(np.diff(qptr) == 0)[0]]
+        raise IddgcnError(f"triple {tuple(int(x) for x in bad)} has no entry in its computation graph: the "
+                          "relation-ratio loss divides 0 by 0 there")
+    levels = mask_schedule(qptr, entry, total, schedule)
+    n_levels = int(levels.max()) if Q else 0
+    order = np.argsort(levels, kind="stable")
+    level_ptr = np.concatenate([[0], np.cumsum(np.bincount(levels, minlength=n_levels + 1)[1:])])
+    row, col, rel_all, _ = _entry_table(dadj)
+
+    g = lambda x, dt: torch.as_tensor(np.ascontiguousarray(x, dtype=dt), device=dev)  # noqa: E731
+    if optimizer is None:
+        lr, b1, b2, eps, it0 = learning_rate, 0.9, 0.999, 1e-7, 0
+        m = torch.zeros(total, dtype=torch.float32, device=dev)
+        v = torch.zeros(total, dtype=torch.float32, device=dev)
+    else:
+        lr, b1, b2, eps, it0 = optimizer.lr, optimizer.b1, optimizer.b2, optimizer.eps, optimizer.iterations
+        if tuple(optimizer.m.shape) != (R, N, N):
+            raise IddgcnError(f"optimizer state must be {(R, N, N)}, got {tuple(optimizer.m.shape)}")
+        flat = g(rel_all * N * N + row * N + col, np.int64)
+        m, v = optimizer.m.view(-1)[flat].contiguous(), optimizer.v.view(-1)[flat].contiguous()
+    steps = torch.zeros(total, dtype=torch.int32, device=dev)
+    n_steps = Q * num_epochs
+    alpha = g(mask_adam_alphas(lr, b1, b2, it0 + 1, n_steps), np.float32)
+    out = torch.empty(len(entry), dtype=torch.float32, device=dev)
+    d_qptr, d_entry = g(qptr, np.int64), g(entry, np.int32)
+    if Q:
+        K, S, Wa, ba = (tuple(params[f"{nm}{l}"] for l in (1, 2, 3)) for nm in ("K", "S", "Wa", "ba"))
+        eng.finish_pending()
+        ev = None
+        if stats is not None:
+            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            ev[0].record()
+        with eng._mark("mask_explain"):
+            ops.mask_explain(params["E"], K, S, Wa, ba, params["rel"], g(triples[:, 0], np.int32),
+                             g(triples[:, 1], np.int32), g(triples[:, 2], np.int32), d_qptr, d_entry,
+                             g(crel, np.int32), g(ccol, np.int32), g(crole, np.int32), g(init[row, col], np.float32),
+                             m, v, steps, alpha, out, g(order, np.int32), level_ptr, num_epochs, 0, b1, b2, eps,
+                             None if target_ratios is None else g(target_ratios, np.float32))
+        if ev is not None:
+            ev[1].record()
+            stats.update(launch_events=ev)
+    if stats is not None:
+        stats.update(levels=n_levels, candidates=int(len(entry)))
+    if optimizer is not None:
+        # what the dense optimizer holds after n_steps more steps: every moment decayed, the touched entries'
+        # (decayed from their last step to the end) scattered back
+        f32 = lambda x: torch.tensor(float(np.float32(x)), dtype=torch.float32, device=dev)  # noqa: E731
+        gap = (n_steps - steps).to(torch.float32)
+        optimizer.m.mul_(float(np.float32(b1)) ** n_steps)
+        optimizer.v.mul_(float(np.float32(b2)) ** n_steps)
+        optimizer.m.view(-1)[flat] = m * torch.pow(f32(b1), gap)
+        optimizer.v.view(-1)[flat] = v * torch.pow(f32(b2), gap)
+        optimizer.iterations = it0 + n_steps
+
+    preds, scores, finals = [], [], []
+    k = int(top_k)
+    entry64 = entry.astype(np.int64)
+    if Q and len(entry) and 1 <= k <= TOPK_MAX:
+        # the selection on the device: drop what the threshold or the (0,0)-only rule rejects, then the segment top-k
+        q_of = np.repeat(np.arange(Q), np.diff(qptr))
+        seg = g(q_of * R + crel, np.int64)
+        kept = out > threshold
+        n_kept = torch.bincount(seg[kept], minlength=Q * R)
+        is00 = g((row[entry64] == 0) & (col[entry64] == 0), np.bool_)
+        score = torch.where(kept & ~(is00 & (n_kept[seg] == 1)), out, torch.full_like(out, -np.inf))
+        te, tv, _ = ops.explain_topk(d_qptr, d_entry, score, k)
+        te, tv = te.cpu().numpy().astype(np.int64), tv.cpu().numpy()
+        for q in range(Q):
+            ok = tv[q] > -np.inf
+            e = te[q][ok]
+            preds.append(np.stack([row[e], rel_all[e], col[e]], 1).reshape(-1, 3))
+            scores.append(tv[q][ok])
+        vals = out.cpu().numpy() if return_masks else None
+    else:
+        vals = out.cpu().numpy()
+        for q in range(Q):
+            a, b = qptr[q], qptr[q + 1]
+            p_, s_ = select_candidates(entry64[a:b], crel[a:b], vals[a:b], row, col, R, threshold, max(k, 0))
+            preds.append(p_)
+            scores.append(s_)
+    if return_masks:
+        finals = [masks_layout(crel[qptr[q]:qptr[q + 1]], vals[qptr[q]:qptr[q + 1]], R) for q in range(Q)]
+    return (preds, scores, finals) if return_masks else (preds, scores)
+
+
+def gnn_explainer_batched(model, adjacency_data, test_triples, num_epochs=5, learning_rate=1e-3, threshold=0.2, **kw):
+    """gnn_explainer's defaults on the batched path."""
+    return mask_explainer_batched(model, adjacency_data, test_triples, num_epochs=num_epochs,
+                                  learning_rate=learning_rate, threshold=threshold, **kw)
+
+
+def iddgcn_explainer_batched(model, adjacency_data, test_triples, num_epochs=10, learning_rate=1e-3, threshold=0.15,
+                             target_ratios=(0.4, 0.4, 0.1, 0.1), **kw):
+    """iddgcn_explainer's defaults on the batched path."""
+    if len(target_ratios) != model.num_relations:
+        raise IddgcnError("target_ratios needs one entry per relation")
+    return mask_explainer_batched(model, adjacency_data, test_triples, num_epochs=num_epochs,
+                                  learning_rate=learning_rate, threshold=threshold, target_ratios=target_ratios, **kw)
 
 
 def explanation_metrics(preds, gt, top=5, exp_num=10):

@@ -919,3 +919,89 @@ def explain_topk(qptr, entry, grad, k, topk_entry=None, topk_val=None, n_pos=Non
     L.check(L.lib().iddgcn_explain_topk_f32(_stream(), Q, k, _ptr(qptr), _ptr(entry), _ptr(grad), _ptr(topk_entry),
                                             _ptr(topk_val), _ptr(n_pos)), "explain_topk")
     return topk_entry, topk_val, n_pos
+
+
+# -- batched mask explainers (include/iddgcn_explain.h) -------------------------------------------
+def mask_explain(E, K, S, Wa, ba, rel, h, r, t, qptr, entry, crel, ccol, crole, init_e, m, v, steps, alpha, out,
+                 qids, level_ptr, num_epochs, epochs_base=0, b1=0.9, b2=0.999, eps=1e-7, target_ratios=None):
+    """Every epoch of the mask training of Q triples (iddgcn_mask_explain_f32), one launch per level: launch i runs
+    the queries qids[level_ptr[i]:level_ptr[i + 1]], one workgroup each; two queries of a level must share no entry,
+    and queries that share one must sit in ascending levels in input order (explain.mask_schedule) — stream order is
+    the only synchronisation.  E (N, D); K, S, Wa, ba: the three layers' (R, D, D), (D, D), (D, R), (R,); rel (R, D);
+    h, r, t (Q,) int32; qptr (Q + 1,) int64 and entry / crel / ccol / crole (qptr[-1],) int32: explain.mask_candidates'
+    lists; init_e, m, v (fp32), steps (int32): one value per stored entry of the full adjacency, m / v / steps
+    updated in place; alpha: one fp32 per global step, read at epochs_base + q * num_epochs + epoch; out (qptr[-1],)
+    receives the final masked values; target_ratios (R,) fp32 or None; level_ptr: a host sequence.
+    D in {32, 64}, 1 <= R <= 8.  Index values are the caller's to validate (IDDGCN_CHECK_INDICES=1 checks them here)."""
+    N, D = E.shape
+    R = rel.shape[0]
+    Q = h.shape[0]
+    num_epochs, epochs_base = int(num_epochs), int(epochs_base)
+    if num_epochs < 0 or epochs_base < 0:
+        raise L.IddgcnError("mask_explain: num_epochs and epochs_base must be non-negative")
+    _req(E, _F32, (N, D), "E")
+    _req(rel, _F32, (R, D), "rel")
+    if not (len(K) == len(S) == len(Wa) == len(ba) == 3):
+        raise L.IddgcnError("mask_explain: K, S, Wa, ba must hold the three layers")
+    for l in range(3):
+        _req(K[l], _F32, (R, D, D), f"K{l + 1}")
+        _req(S[l], _F32, (D, D), f"S{l + 1}")
+        _req(Wa[l], _F32, (D, R), f"Wa{l + 1}")
+        _req(ba[l], _F32, (R,), f"ba{l + 1}")
+        if K[l] is None or S[l] is None or Wa[l] is None or ba[l] is None:
+            raise L.IddgcnError("mask_explain: every layer's K, S, Wa, ba is required")
+    _idx_ok(h, Q, N, "h")
+    _idx_ok(r, Q, R, "r")
+    _idx_ok(t, Q, N, "t")
+    _req(qptr, torch.int64, (Q + 1,), "qptr")
+    C = entry.shape[0]
+    total = m.shape[0]
+    _idx_ok(entry, C, total, "entry")
+    _idx_ok(crel, C, R, "crel")
+    _idx_ok(ccol, C, N, "ccol")
+    _idx_ok(crole, C, 4, "crole")
+    _req(init_e, _F32, (total,), "init_e")
+    _req(m, _F32, (total,), "m")
+    _req(v, _F32, (total,), "v")
+    _req(steps, _I32, (total,), "steps")
+    _req(out, _F32, (C,), "out")
+    _req(alpha, _F32, None, "alpha")
+    if alpha.dim() != 1 or alpha.shape[0] < epochs_base + Q * num_epochs:
+        raise L.IddgcnError("mask_explain: alpha needs one entry per global step (epochs_base + Q * num_epochs)")
+    if target_ratios is not None:
+        _req(target_ratios, _F32, (R,), "target_ratios")
+    nq = qids.shape[0]
+    _idx_ok(qids, nq, Q, "qids")
+    lp = [int(x) for x in level_ptr]
+    if not lp or lp[0] < 0 or lp[-1] > nq or any(b < a for a, b in zip(lp, lp[1:])):
+        raise L.IddgcnError("mask_explain: level_ptr must ascend within [0, len(qids)]")
+    if E.data_ptr() & 15:
+        raise L.IddgcnError("mask_explain: E must be 16-byte aligned")
+    if CHECK_INDEX_RANGES and Q:
+        qp = qptr.cpu()
+        if int(qp[0]) != 0 or bool((qp[1:] < qp[:-1]).any()) or int(qp[-1]) != C:
+            raise L.IddgcnError("mask_explain: qptr must ascend from 0 to len(entry)")
+    a = L.MaskExplainArgs()
+    a.N, a.d, a.R, a.num_epochs, a.epochs_base = N, D, R, num_epochs, epochs_base
+    a.h, a.r, a.t, a.qptr = h.data_ptr(), r.data_ptr(), t.data_ptr(), qptr.data_ptr()
+    a.entry, a.crel, a.ccol, a.crole = entry.data_ptr(), crel.data_ptr(), ccol.data_ptr(), crole.data_ptr()
+    a.E, a.rel = E.data_ptr(), rel.data_ptr()
+    # the backward reads K^l_r^T and S^l^T along rows: transposed copies, made once per call
+    KT = [x.transpose(1, 2).contiguous() for x in K]
+    ST = [x.t().contiguous() for x in S]
+    for l in range(3):
+        a.K[l], a.S[l], a.Wa[l], a.ba[l] = K[l].data_ptr(), S[l].data_ptr(), Wa[l].data_ptr(), ba[l].data_ptr()
+        a.KT[l], a.ST[l] = KT[l].data_ptr(), ST[l].data_ptr()
+    a.init_e, a.m, a.v, a.steps, a.alpha = init_e.data_ptr(), m.data_ptr(), v.data_ptr(), steps.data_ptr(), \
+        alpha.data_ptr()
+    a.b1, a.b2, a.eps = float(b1), float(b2), float(eps)
+    a.target_ratios = None if target_ratios is None else target_ratios.data_ptr()
+    a.out = out.data_ptr()
+    fn, st = L.lib().iddgcn_mask_explain_f32, _stream()
+    for lo, hi in zip(lp, lp[1:]):
+        if hi == lo:
+            continue
+        a.qids = qids.data_ptr() + 4 * lo
+        a.n_queries = hi - lo
+        L.check(fn(st, ctypes.byref(a)), "mask_explain")
+    return out

@@ -65,6 +65,65 @@ int iddgcn_explain_row_grads_f32(void* stream, int Q, int N, int d, int R, const
 int iddgcn_explain_topk_f32(void* stream, int Q, int k, const long long* qptr, const int* entry, const float* grad,
                             int* topk_entry, float* topk_val, int* n_pos);
 
+/*
+ * Batched mask explainers (GNNExplainer / the IDDGCN explainer): every epoch of one triple's mask training in one
+ * workgroup.  The computation graph of (h, r, t) is every stored entry whose row or column is h or t; its rows h and
+ * t are the full graph's rows h and t, and the prediction reads A_r only through AE_r[h] and AE_r[t].  A query's
+ * candidates j = 0 .. n-1 (ascending entry id of the full adjacency, all of base value 1) carry rel_j, col_j and
+ * role_j (bit 0: the entry's row is h, bit 1: it is t, 0: only its column is h or t).  Per query, with
+ * step0 = epochs_base + q * num_epochs (q = the query's place in the INPUT order: the shared optimizer's count):
+ *
+ *     load:   e = entry_j;  gap = step0 - steps[e];  m[e] *= b1^gap;  v[e] *= b2^gap;  mask_j = init_e[e]
+ *     before = forward(mv = 1)
+ *     for ep = 0 .. num_epochs-1:
+ *         mv_j = sigmoid(mask_j);   AE_r[h] = sum_{role_j & 1, rel_j = r} mv_j E[col_j]  (j ascending), AE_r[t] alike
+ *         forward:  xh^0 = E[h], xt^0 = E[t];  for l = 1, 2, 3:
+ *             a_l = softmax(xh^{l-1} Walpha^l + balpha^l),  w_l = sigmoid(a_l),  P^l_r[.] = AE_r[.] K^l_r
+ *             xh^l = sigmoid(xh^{l-1} S^l + sum_r w_lr P^l_r[h]),  xt^l = sigmoid(xt^{l-1} S^l + sum_r w_lr P^l_r[t])
+ *             p = sigmoid(sum_d xh^3 rel[r] xt^3)
+ *         backward: the one above with scale = 1, P^l_r[h], P^l_r[t] the local ones and the layer-1 S = S^1 unused
+ *         g_j = (<GH_rel_j, E[col_j]> [role_j & 1] + <GT_rel_j, E[col_j]> [role_j & 2]) * (-before / (p + 1e-5))
+ *         with target_ratios (R values):  c_r = sum_{rel_j = r} mv_j,  C = sum_r c_r,  ratio_r = c_r / C,
+ *             dr_r = 2 (ratio_r - target_r) / R,  gs_r = (dr_r - sum_i dr_i ratio_i) / C,  g_j = (g_j + gs_rel_j) / 2
+ *         g_j = g_j mv_j (1 - mv_j)
+ *         Adam, dense form, on e = entry_j:  m += (g - m)(1 - b1);  v += (g^2 - v)(1 - b2)
+ *             mask_j -= m alpha[step0 + ep] / (sqrt(v) + eps)
+ *     finish: out[qptr[q] + j] = sigmoid(mask_j);  steps[e] = step0 + num_epochs
+ *
+ * m, v, steps hold one value per stored entry of the full adjacency: the moments of the reference's one shared
+ * optimizer, decayed lazily over the steps an entry sat out.  One launch runs the queries qids[0 .. n_queries); two
+ * queries of one launch must share no entry (explain.mask_schedule), queries that share one run in input order in
+ * successive launches of one stream.  No atomics, no flags; every sum has a fixed order that depends on the query's
+ * own candidates only.
+ */
+typedef struct {
+    int N, d, R;
+    int num_epochs, epochs_base;
+    int n_queries;
+    const int* qids;                 /* (n_queries) query ids of this launch */
+    const int* h; const int* r; const int* t;                 /* per query, int32, validated by the caller */
+    const long long* qptr;           /* (Q + 1) candidate segments */
+    const int* entry; const int* crel; const int* ccol; const int* crole;   /* per candidate */
+    const float* E;                  /* (N, d), 16-byte aligned */
+    const float* K[3];               /* (R, d, d) */
+    const float* KT[3];              /* (R, d, d): every K^l_r transposed (the backward reads it along rows) */
+    const float* S[3];               /* (d, d) */
+    const float* ST[3];              /* (d, d): S^l transposed (ST[0] is never read) */
+    const float* Wa[3];              /* (d, R) */
+    const float* ba[3];              /* (R) */
+    const float* rel;                /* (R, d) */
+    const float* init_e;             /* (total_nnz) init_value[row, col] of every stored entry */
+    float* m; float* v; int* steps;  /* (total_nnz) each */
+    const float* alpha;              /* one per global step */
+    float b1, b2, eps;
+    const float* target_ratios;      /* (R) or null */
+    float* out;                      /* (qptr[Q]) final masked values; the masks live here while a query trains */
+} iddgcn_mask_explain_t;
+
+/* d in {32, 64} (IDDGCN_E_BAD_DIM), 1 <= R <= 8 (IDDGCN_E_BAD_REL), n_queries >= 0 (0: nothing launched),
+ * num_epochs >= 0; a null pointer (target_ratios excepted) or a misaligned E: IDDGCN_E_BAD_ARG. */
+int iddgcn_mask_explain_f32(void* stream, const iddgcn_mask_explain_t* args);
+
 #ifdef __cplusplus
 }
 #endif
