@@ -2693,12 +2693,19 @@ __global__ __launch_bounds__(512) void gemm_tn256_b3_kernel(long long M_, long l
 // Workgroup pair per row range (column half h = 0, 1; blockIdx 8 apart: the same XCD, so the pair's second read of a
 // dO tile is an L2 hit), as sigma_tn_bf16_kernel: workgroup h reads dO (all columns) and X[:, half h], and writes
 // dX[:, half h] over the same bytes, so the in-place write never meets the other workgroup's reads.
-//   * sigma': wave w owns output columns c0 = 128h + 16w .. +15; S^T as three bf16 planes is operand A of
+// Twelve waves, three per SIMD (768 threads, at most 168 VGPRs, round 11): waves 0-7 are the sigma' column groups and do
+// every chore (DMA, conversion, epilogue stores), waves 8-11 (one per SIMD) run dS MFMAs alone between two barriers, so
+// the MFMA pipe has work while the sigma' waves of its SIMD stage, convert or store.
+//   * sigma': wave w < 8 owns output columns c0 = 128h + 16w .. +15; S^T as three bf16 planes is operand A of
 //     v_mfma_f32_16x16x32_bf16 (96 VGPRs), the dO planes operand B (ds_read_b128): rowgemm256_b3_kernel's six
 //     products in its order, so dX is bitwise that kernel's.  Epilogue x(1 - x) with x = p0 + p1 + p2 rebuilt (exactly:
 //     the pieces are an exact split) from the X planes in LDS.
-//   * dS[half h rows, :]: wave w owns X columns 128h + 32(w & 3) .. +31 x dO columns 128(w >> 2) .. +127 as 2 x 8
-//     16x16 tiles (64 VGPRs); v_mfma_f32_16x16x32_bf16 over the tile's 32 rows (one k-step) on ds_read_b64_tr_b16
+//   * dS[half h rows, :] as 8 x 16 16x16 tiles, each owned by one wave for the whole launch (a tile's value does not
+//     depend on its owner): TN wave 8 + g owns X columns 128h + 32g .. +31 x dO column blocks 0 .. NBT - 1 (2 x 12
+//     tiles, 96 VGPRs, dO fragments double-buffered); sigma' wave w owns, of the same X columns (g = w & 3), dO blocks
+//     NBT + 2(w >> 2), + 1 (2 x 2 tiles, 16 VGPRs), after its epilogue.  All sixteen blocks on the TN waves (128
+//     VGPRs) leave no room for a second fragment set and measured slower than two waves per SIMD (profiles/r11).
+//     v_mfma_f32_16x16x32_bf16 over the tile's 32 rows (one k-step) on ds_read_b64_tr_b16
 //     fragments (T10 geometry: lane l supplies row 8(l >> 4) + ((l >> 2) & 3) (+4), columns 4(l & 3) .. +3 of a
 //     16-column block); per 16x16 tile the five smaller products start from zero and join the running sum by one fp32
 //     add in front of the a0 b0 MFMA (gemm_tn256_b3_kernel's accuracy form, 32 rows per join).
@@ -2708,10 +2715,16 @@ __global__ __launch_bounds__(512) void gemm_tn256_b3_kernel(long long M_, long l
 // 512 j / 256 j of the slot) with 16-B chunk c of row r at c ^ stn_sw(r).  Every slot starts at bank 0, so the
 // conflict analysis of sigma_tn_bf16_kernel's 512 / 256-B slots holds for the ds_read_b128 row fragments and the
 // transposed reads alike.  Tile t + 1 is DMA'd while tile t computes and converted after its MFMAs, both by waves 0-3
-// for their SIMD's two waves (waves 4-7: MFMAs and epilogue only); one barrier per tile.  Every LDS read of the loop
+// for their SIMD's two sigma' waves (waves 4-7: MFMAs and epilogue only); one barrier of all twelve waves per tile.  Every LDS read of the loop
 // is issued in asm with a tied lgkmcnt wait (no compiler vmcnt drain of the DMAs).
 namespace st3 {
 constexpr int D = 256, TR = 32, DP = 1536, XP = 768, DOB = TR * DP, XB = TR * XP, BUF = DOB + XB, NBUF = 2;
+// of the sixteen 16-column dO blocks of a dS row, the first NBT belong to the TN waves, the other four to the sigma' waves
+constexpr int NBT = 12;
+template <int N>
+struct ic {
+    static constexpr int v = N;
+};
 }  // namespace st3
 // three transposed reads at a, a + PS, a + 2 PS (the three planes of one 4-row block).  Every multi-instruction asm
 // read here marks its outputs early-clobber ("=&v"): without it the compiler may give an output the input address
@@ -2732,7 +2745,7 @@ __device__ __forceinline__ float bf_at(const u32x2& v, int q) {
     const unsigned w = v[q >> 1];
     return __builtin_bit_cast(float, (q & 1) ? (w & 0xffff0000u) : (w << 16));
 }
-__global__ __launch_bounds__(512) void sigma_tn_b3_kernel(long long M, int tiles_per_block, int n_ranges,
+__global__ __launch_bounds__(768) void sigma_tn_b3_kernel(long long M, int tiles_per_block, int n_ranges,
                                                           const float* __restrict__ dO, float* __restrict__ X,
                                                           const float* __restrict__ S, float* __restrict__ slab) {
     using namespace st3;
@@ -2748,7 +2761,8 @@ __global__ __launch_bounds__(512) void sigma_tn_b3_kernel(long long M, int tiles
     const long long t_beg = (long long)range * tiles_per_block;
     long long t_end = t_beg + tiles_per_block;
     if (t_end > ntiles) t_end = ntiles;            // a range past the table still writes its (zero) partial
-    const int i16 = lane & 15, g = lane >> 4;
+    // the trip count as a scalar (the 64-bit minimum is VALU work: its result stayed in a VGPR pair across the loop)
+    const int n_t = __builtin_amdgcn_readfirstlane(t_end > t_beg ? (int)(t_end - t_beg) : 0);
     const int c0 = 128 * half + 16 * wave;
     const unsigned lds0 = lds_u32(lds);
     // a lane index the compiler cannot hoist out of the loop: the per-lane LDS offsets of every phase are recomputed
@@ -2760,22 +2774,9 @@ __global__ __launch_bounds__(512) void sigma_tn_b3_kernel(long long M, int tiles
     };
 
     // S^T as operand A: column c0 + i16, k = 32q + 8g + e, split exactly into three bf16 pieces
-    bf16x8 w0[8], w1[8], w2[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            __bf16 a, b, c;
-            split3(S[(c0 + i16) * D + 32 * q + 8 * g + e], a, b, c);
-            w0[q][e] = a;
-            w1[q][e] = b;
-            w2[q][e] = c;
-        }
-    f32x4 tacc[2][8];
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-        for (int nb = 0; nb < 8; ++nb) tacc[mb][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // (sigma' waves 0-7 only; the TN waves 8-11 hold the dS accumulators instead)
+    const bool tn_wave = wave >= 8;
+    bf16x8 w0[8], w1[8], w2[8];             // filled below, once the TN waves have branched off
 
     // fp32 rows of tile t into buffer bb: dO rows 4w .. 4w+3 (one full-wave DMA each), X-half rows 4w .. 4w+3 (a pair
     // per full-wave DMA); rows past M as fp32 zeros (0 x whatever-bits could be NaN in the TN).  Returns the DMA count.
@@ -2859,66 +2860,72 @@ __global__ __launch_bounds__(512) void sigma_tn_b3_kernel(long long M, int tiles
     auto mfma_sigma = [&](int bb, f32x4 (&acc)[2]) __attribute__((always_inline)) {
         const int lane = fresh_lane();
         const int i16 = lane & 15, g = lane >> 4, swi = stn_sw(i16), sa = swi >> 2, sl = swi & 3;
-        const unsigned rb0 = lds0 + bb * BUF + i16 * DP + 16 * (g ^ sl);
-        const unsigned ad0 = rb0 + 64 * (0 ^ sa), ad1 = rb0 + 64 * (1 ^ sa), ad2 = rb0 + 64 * (2 ^ sa),
-                       ad3 = rb0 + 64 * (3 ^ sa);
+        // one address register for the eight k-steps: 64 ((q & 3) ^ sa) = (64 sa) ^ 64 (q & 3), and DP = 3 << 9 leaves bits
+        // 6-7 of the row offset free; each k-step's address is re-derived from an opaque copy (the four kept live spilled)
+        const unsigned sb = lds0 + bb * BUF, rb0 = i16 * DP + 16 * (g ^ sl) + 64 * sa;
+        auto adq = [&](int q) __attribute__((always_inline)) {
+            unsigned r = rb0;
+            asm volatile("" : "+v"(r));
+            return sb + 256 * (q >> 2) + (r ^ (64 * (q & 3)));
+        };
         f32x4 hi0 = {0.f, 0.f, 0.f, 0.f}, lo0 = hi0, hi1 = hi0, lo1 = hi0;
-        u32x4 fx[2][3], fy[2][3];
+        // Fragments of rows i16 (x) and 16 + i16 (y), one register set per plane (24 VGPRs: beside the weights and the
+        // wave's own dS tiles two sets, 48, do not fit at three waves per SIMD, and a second set for plane 0 alone
+        // spilled).  Step q + 1's planes follow step q's MFMAs plane by plane: plane 2 as soon as its two MFMAs (the
+        // first) have issued, plane 1 after the 8th, plane 0 after the last; one wait at the top of the step.
+        u32x4 x0, y0, x1, y1, x2, y2;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#define ST3_LOADQ(Q, S_, AD)                                                                              \
-        asm volatile("ds_read_b128 %0, %6 offset:%7\n\tds_read_b128 %1, %6 offset:%8\n\t"                 \
-                     "ds_read_b128 %2, %6 offset:%9\n\tds_read_b128 %3, %6 offset:%10\n\t"                \
-                     "ds_read_b128 %4, %6 offset:%11\n\tds_read_b128 %5, %6 offset:%12"                   \
-                     : "=&v"(fx[S_][0]), "=&v"(fx[S_][1]), "=&v"(fx[S_][2]), "=&v"(fy[S_][0]), "=&v"(fy[S_][1]),  \
-                       "=&v"(fy[S_][2])                                                                  \
-                     : "v"(AD), "i"(256 * ((Q) >> 2)), "i"(256 * ((Q) >> 2) + 512),                       \
-                       "i"(256 * ((Q) >> 2) + 1024), "i"(256 * ((Q) >> 2) + 16 * DP),                     \
-                       "i"(256 * ((Q) >> 2) + 16 * DP + 512), "i"(256 * ((Q) >> 2) + 16 * DP + 1024)      \
-                     : "memory")
-        ST3_LOADQ(0, 0, ad0);
+#define ST3_LD2(DX, DY, AD, OFF)                                                                               \
+        do {                                                                                                   \
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DX) : "v"(AD), "i"(OFF) : "memory");           \
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DY) : "v"(AD), "i"((OFF) + 16 * DP) : "memory"); \
+        } while (0)
+        {
+            const unsigned ad = adq(0);
+            ST3_LD2(x0, y0, ad, 0);
+            ST3_LD2(x2, y2, ad, 1024);
+            ST3_LD2(x1, y1, ad, 512);
+        }
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-            const int S_ = q & 1;
-            if (q + 1 < 8) {
-                switch (q) {      // the offsets are immediates: one asm per k-step
-                    case 0: ST3_LOADQ(1, 1, ad1); break;
-                    case 1: ST3_LOADQ(2, 0, ad2); break;
-                    case 2: ST3_LOADQ(3, 1, ad3); break;
-                    case 3: ST3_LOADQ(4, 0, ad0); break;
-                    case 4: ST3_LOADQ(5, 1, ad1); break;
-                    case 5: ST3_LOADQ(6, 0, ad2); break;
-                    default: ST3_LOADQ(7, 1, ad3); break;
-                }
-                asm volatile("s_waitcnt lgkmcnt(6)"
-                             : "+v"(fx[S_][0]), "+v"(fx[S_][1]), "+v"(fx[S_][2]), "+v"(fy[S_][0]), "+v"(fy[S_][1]),
-                               "+v"(fy[S_][2])::"memory");
-            } else {
-                asm volatile("s_waitcnt lgkmcnt(0)"
-                             : "+v"(fx[S_][0]), "+v"(fx[S_][1]), "+v"(fx[S_][2]), "+v"(fy[S_][0]), "+v"(fy[S_][1]),
-                               "+v"(fy[S_][2])::"memory");
-            }
-            const bf16x8 x0 = __builtin_bit_cast(bf16x8, fx[S_][0]), x1 = __builtin_bit_cast(bf16x8, fx[S_][1]),
-                         x2 = __builtin_bit_cast(bf16x8, fx[S_][2]);
-            const bf16x8 y0 = __builtin_bit_cast(bf16x8, fy[S_][0]), y1 = __builtin_bit_cast(bf16x8, fy[S_][1]),
-                         y2 = __builtin_bit_cast(bf16x8, fy[S_][2]);
-            lo0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[q], x2, lo0, 0, 0, 0);
-            lo1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[q], y2, lo1, 0, 0, 0);
-            lo0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2[q], x0, lo0, 0, 0, 0);
-            lo1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2[q], y0, lo1, 0, 0, 0);
-            lo0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1[q], x1, lo0, 0, 0, 0);
-            lo1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1[q], y1, lo1, 0, 0, 0);
-            lo0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[q], x1, lo0, 0, 0, 0);
-            lo1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[q], y1, lo1, 0, 0, 0);
-            lo0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1[q], x0, lo0, 0, 0, 0);
-            lo1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1[q], y0, lo1, 0, 0, 0);
-            hi0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[q], x0, hi0, 0, 0, 0);
-            hi1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[q], y0, hi1, 0, 0, 0);
+            const bool more = q + 1 < 8;
+            const unsigned nad = adq(more ? q + 1 : q);
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(x0), "+v"(y0), "+v"(x2), "+v"(y2), "+v"(x1), "+v"(y1)::"memory");
+            const bf16x8 fx0 = __builtin_bit_cast(bf16x8, x0), fy0 = __builtin_bit_cast(bf16x8, y0);
+            const bf16x8 fx1 = __builtin_bit_cast(bf16x8, x1), fy1 = __builtin_bit_cast(bf16x8, y1);
+            lo0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[q], __builtin_bit_cast(bf16x8, x2), lo0, 0, 0, 0);
+            lo1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[q], __builtin_bit_cast(bf16x8, y2), lo1, 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (more) ST3_LD2(x2, y2, nad, 1024);
+            lo0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2[q], fx0, lo0, 0, 0, 0);
+            lo1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2[q], fy0, lo1, 0, 0, 0);
+            lo0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1[q], fx1, lo0, 0, 0, 0);
+            lo1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1[q], fy1, lo1, 0, 0, 0);
+            lo0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[q], fx1, lo0, 0, 0, 0);
+            lo1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[q], fy1, lo1, 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (more) ST3_LD2(x1, y1, nad, 512);
+            lo0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1[q], fx0, lo0, 0, 0, 0);
+            lo1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1[q], fy0, lo1, 0, 0, 0);
+            hi0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[q], fx0, hi0, 0, 0, 0);
+            hi1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[q], fy0, hi1, 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (more) ST3_LD2(x0, y0, nad, 0);
         }
-#undef ST3_LOADQ
+#undef ST3_LD2
         acc[0] = hi0 + lo0;
         acc[1] = hi1 + lo1;
     };
-    auto mfma_tn = [&](int bb) __attribute__((always_inline)) {
+    // dS tiles of X columns 128h + 32 xg .. +31 (two 16-column blocks mb) x the NB dO column blocks nb0 .. nb0 + NB - 1:
+    // v_mfma_f32_16x16x32_bf16 over the tile's 32 rows on transposed-read fragments, two chains (mb = 0, 1) interleaved;
+    // per 16x16 tile the five smaller products start from zero and join the running sum by one fp32 add in front of the
+    // a0 b0 MFMA.  DB: the dO fragments of block i + 1 are read into a second register set while block i's MFMAs run
+    // (the TN waves); without it they follow block i's MFMAs into the same set (the sigma' waves' four tiles, which
+    // have no room for two).  Every wait is a full one (tests/test_host.py lets nothing name a transposed read's
+    // destination before lgkmcnt(0)).
+    auto mfma_tn = [&](int bb, int xg, int nb0, auto nbc, auto dbc, auto& tacc) __attribute__((always_inline)) {
+        constexpr int NB = decltype(nbc)::v;
+        constexpr bool DB = decltype(dbc)::v != 0;
         // transposed-read rows of this lane (first / second read of a fragment) and their swizzles; the byte of the
         // lane's 4 columns in a row of 16-column block blk is 16 ((2 blk) ^ (sw & 14)) + 16 (tb ^ (sw & 1)) + 8 (l & 1)
         const int lane = fresh_lane();
@@ -2927,19 +2934,19 @@ __global__ __launch_bounds__(512) void sigma_tn_b3_kernel(long long M, int tiles
         const int tb = (lane & 3) >> 1;
         const unsigned xoa = tra * XP + 16 * (tb ^ (swa & 1)) + 8 * (lane & 1),
                        xoq = trq * XP + 16 * (tb ^ (swq & 1)) + 8 * (lane & 1);
-        const unsigned doa = tra * DP + 16 * (tb ^ (swa & 1)) + 8 * (lane & 1) + 256 * (wave >> 2),
-                       doq = trq * DP + 16 * (tb ^ (swq & 1)) + 8 * (lane & 1) + 256 * (wave >> 2);
+        const unsigned doa = tra * DP + 16 * (tb ^ (swa & 1)) + 8 * (lane & 1),
+                       doq = trq * DP + 16 * (tb ^ (swq & 1)) + 8 * (lane & 1);
         const int swa_e = swa & 14, swq_e = swq & 14;
         const unsigned db = lds0 + bb * BUF, xb = db + DOB;
         v4s16 xa[2][2][3], fb[2][2][3];
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb) {
-            const int cx = 4 * (wave & 3) + 2 * mb;
+            const int cx = 4 * xg + 2 * mb;
             tr_read3<256>(xa[mb][0], xb + xoa + 16 * (cx ^ swa_e));
             tr_read3<256>(xa[mb][1], xb + xoq + 16 * (cx ^ swq_e));
         }
-        tr_read3<512>(fb[0][0], db + doa + 16 * (0 ^ swa_e));
-        tr_read3<512>(fb[0][1], db + doq + 16 * (0 ^ swq_e));
+        tr_read3<512>(fb[0][0], db + doa + 16 * ((2 * nb0) ^ swa_e));
+        tr_read3<512>(fb[0][1], db + doq + 16 * ((2 * nb0) ^ swq_e));
         asm volatile("s_waitcnt lgkmcnt(0)"
                      : "+v"(xa[0][0][0]), "+v"(xa[0][0][1]), "+v"(xa[0][0][2]), "+v"(xa[0][1][0]), "+v"(xa[0][1][1]),
                        "+v"(xa[0][1][2]), "+v"(xa[1][0][0]), "+v"(xa[1][0][1]), "+v"(xa[1][0][2]), "+v"(xa[1][1][0]),
@@ -2951,11 +2958,12 @@ __global__ __launch_bounds__(512) void sigma_tn_b3_kernel(long long M, int tiles
 #pragma unroll
             for (int j = 0; j < 3; ++j) a[mb][j] = cat_tr(xa[mb][0][j], xa[mb][1][j]);
 #pragma unroll
-        for (int nb = 0; nb < 8; ++nb) {
-            const int s = nb & 1;
-            if (nb + 1 < 8) {
-                tr_read3<512>(fb[s ^ 1][0], db + doa + 16 * ((2 * (nb + 1)) ^ swa_e));
-                tr_read3<512>(fb[s ^ 1][1], db + doq + 16 * ((2 * (nb + 1)) ^ swq_e));
+        for (int i = 0; i < NB; ++i) {
+            const int s = DB ? (i & 1) : 0, sn = DB ? (s ^ 1) : 0;
+            const bool more = i + 1 < NB;
+            if (DB && more) {
+                tr_read3<512>(fb[sn][0], db + doa + 16 * ((2 * (nb0 + i + 1)) ^ swa_e));
+                tr_read3<512>(fb[sn][1], db + doq + 16 * ((2 * (nb0 + i + 1)) ^ swq_e));
             }
             const bf16x8 b0 = cat_tr(fb[s][0][0], fb[s][1][0]), b1 = cat_tr(fb[s][0][1], fb[s][1][1]),
                          b2 = cat_tr(fb[s][0][2], fb[s][1][2]);
@@ -2970,13 +2978,17 @@ __global__ __launch_bounds__(512) void sigma_tn_b3_kernel(long long M, int tiles
             e1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1][0], b1, e1, 0, 0, 0);
             e0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0][1], b0, e0, 0, 0, 0);
             e1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1][1], b0, e1, 0, 0, 0);
-            tacc[0][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0][0], b0, tacc[0][nb] + e0, 0, 0, 0);
-            tacc[1][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1][0], b0, tacc[1][nb] + e1, 0, 0, 0);
+            tacc[0][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0][0], b0, tacc[0][i] + e0, 0, 0, 0);
+            tacc[1][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1][0], b0, tacc[1][i] + e1, 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-            if (nb + 1 < 8)
+            if (!DB && more) {
+                tr_read3<512>(fb[0][0], db + doa + 16 * ((2 * (nb0 + i + 1)) ^ swa_e));
+                tr_read3<512>(fb[0][1], db + doq + 16 * ((2 * (nb0 + i + 1)) ^ swq_e));
+            }
+            if (more)
                 asm volatile("s_waitcnt lgkmcnt(0)"
-                             : "+v"(fb[s ^ 1][0][0]), "+v"(fb[s ^ 1][0][1]), "+v"(fb[s ^ 1][0][2]), "+v"(fb[s ^ 1][1][0]),
-                               "+v"(fb[s ^ 1][1][1]), "+v"(fb[s ^ 1][1][2])::"memory");
+                             : "+v"(fb[sn][0][0]), "+v"(fb[sn][0][1]), "+v"(fb[sn][0][2]), "+v"(fb[sn][1][0]),
+                               "+v"(fb[sn][1][1]), "+v"(fb[sn][1][2])::"memory");
         }
     };
     // epilogue: dX = acc x(1 - x) (rowgemm256_b3_kernel's order), x rebuilt from the planes of columns 16w + 4g .. +3;
@@ -3013,14 +3025,69 @@ __global__ __launch_bounds__(512) void sigma_tn_b3_kernel(long long M, int tiles
         return 2;
     };
 
-    if (t_beg < t_end) {
+    if (tn_wave) {
+        // TN waves: between two barriers only transposed reads and MFMAs (every read waited for inside mfma_tn); the
+        // accumulators live in this branch alone, so they never share a live range with the sigma' waves' weights
+        f32x4 tacc[2][NBT];
+#pragma unroll
+        for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+            for (int nb = 0; nb < NBT; ++nb) tacc[mb][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (n_t > 0) {
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+        }
+        int b = 0;
+        for (int it = 0; it < n_t; ++it) {
+            mfma_tn(b, wave - 8, 0, ic<NBT>{}, ic<1>{}, tacc);
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            b ^= 1;
+        }
+        // every dS tile of this row half has one owner: rows 32 tw + 16 mb .., columns 16 nb .., nb < NBT here
+        float* out = slab + (long long)range * D * D;
+        const int i16 = fresh_lane() & 15, g = fresh_lane() >> 4;
+#pragma unroll
+        for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+            for (int nb = 0; nb < NBT; ++nb)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int row = 128 * half + 32 * (wave - 8) + 16 * mb + 4 * g + j;
+                    out[row * D + 16 * nb + i16] = tacc[mb][nb][j];
+                }
+        return;
+    }
+    {
+        const int i16 = lane & 15, g = lane >> 4;
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                __bf16 a, b, c;
+                split3(S[(c0 + i16) * D + 32 * q + 8 * g + e], a, b, c);
+                w0[q][e] = a;
+                w1[q][e] = b;
+                w2[q][e] = c;
+            }
+    }
+    // the sigma' waves' own dS tiles: X column group w & 3 (as TN wave 8 + (w & 3)) x dO blocks NBT + 2 (w >> 2), + 1
+    const int own_nb0 = NBT + 2 * (wave >> 2);
+    f32x4 tacc[2][2];
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) tacc[mb][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (n_t > 0) {
         stage(t_beg, 0, wave);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         convert(0, wave);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __syncthreads();
-        // per iteration: the DMA of tile t + 1, the sigma' MFMAs of tile t, its epilogue, its TN MFMAs, then tile t + 1's
-        // conversion once its DMA has landed (only the epilogue's stores younger); one barrier.  Measured and not kept
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        // per iteration: the DMA of tile t + 1, the sigma' MFMAs of tile t, its epilogue, the wave's own four dS tiles, then
+        // tile t + 1's conversion once its DMA has landed (only the epilogue's stores younger); one barrier.  Measured and
+        // not kept in the eight-wave form
         // (round 6, profiles/r06/ab_sigma_tn_b3_r06b.txt): the epilogue and the conversion issued behind the TN MFMAs,
         // one piece per column block (5.24 vs 4.99 ms per config-3 launch), and s_setprio 1 for waves 4-7 of that form
         // (5.25-5.32); waves 4-7 running TN before sigma' (profiles/r06/ab_sigma_tn_b3_r06a.txt: 4.99-5.02 vs 4.78-4.89)
@@ -3030,10 +3097,12 @@ __global__ __launch_bounds__(512) void sigma_tn_b3_kernel(long long M, int tiles
             // run only MFMAs and their epilogue: they start the tile's MFMAs at once and end it with no conversion.
             // 4.83 vs 4.98-5.04 ms per config-3 launch for every wave staging and converting its own rows; the
             // conversions between the epilogue and the TN MFMAs instead of after them 4.89-4.90
-            // (profiles/r06/ab_sigma_tn_roles_r06l.txt, phase stamps in profiles/r06/stamps)
+            // (profiles/r06/ab_sigma_tn_roles_r06l.txt, phase stamps in profiles/r06/stamps).  The same holds beside the TN
+            // waves: every sigma' wave on its own rows 4.64-4.79 vs 4.47-4.63 ms (profiles/r11/ab_sigma_tn_variants.txt)
             const bool stager = wave < 4;
-            for (long long t = t_beg; t < t_end; ++t) {
-                const bool more = t + 1 < t_end;
+            for (int it = 0; it < n_t; ++it) {
+                const long long t = t_beg + it;
+                const bool more = it + 1 < n_t;
                 if (more && stager) {
                     stage(t + 1, b ^ 1, wave);
                     stage(t + 1, b ^ 1, wave + 4);
@@ -3041,7 +3110,7 @@ __global__ __launch_bounds__(512) void sigma_tn_b3_kernel(long long M, int tiles
                 f32x4 acc[2];
                 mfma_sigma(b, acc);
                 const int ns = epilogue(t, b, acc);
-                mfma_tn(b);
+                mfma_tn(b, wave & 3, own_nb0, ic<2>{}, ic<0>{}, tacc);
                 if (more && stager) {
                     wait_vm(ns);
                     convert(b ^ 1, wave);
@@ -3055,14 +3124,15 @@ __global__ __launch_bounds__(512) void sigma_tn_b3_kernel(long long M, int tiles
         }
     }
     float* out = slab + (long long)range * D * D;
+    const int i16 = fresh_lane() & 15, g = fresh_lane() >> 4;
 #pragma unroll
     for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
-        for (int nb = 0; nb < 8; ++nb)
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int row = 128 * half + 32 * (wave & 3) + 16 * mb + 4 * g + j;
-                out[row * D + 128 * (wave >> 2) + 16 * nb + i16] = tacc[mb][nb][j];
+                out[row * D + 16 * (own_nb0 + i) + i16] = tacc[mb][i][j];
             }
 }
 
@@ -5637,7 +5707,7 @@ int iddgcn_sigma_tn_f32(void* stream, long long M, int d, const float* dO, float
     const long long tpb = nt > 0 ? (nt + nr - 1) / nr : 1;
     const long long n = (long long)d * d;
     if (slab_floats < nr * n) return IDDGCN_E_BAD_ARG;
-    hipLaunchKernelGGL(sigma_tn_b3_kernel, dim3((unsigned)(2 * nr)), dim3(512), 0, st, M, (int)tpb, nr, dO, X, S, slab);
+    hipLaunchKernelGGL(sigma_tn_b3_kernel, dim3((unsigned)(2 * nr)), dim3(768), 0, st, M, (int)tpb, nr, dO, X, S, slab);
     int rc = launch_status();
     if (rc) return rc;
     launch_reduce_slabs(st, nr, n, slab, dS, 0, 1.0f);
