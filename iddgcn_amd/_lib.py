@@ -113,6 +113,7 @@ SIGNATURES = {
                                             vp, ci]),
     "iddgcn_tail_seg_reduce_bf16": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, cll, vp, cll, vp, vp]),
     "iddgcn_tail_seg_reduce_head_bf16": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, cll, vp, cll, vp, vp, vp, vp, vp]),
+    "iddgcn_tail_seg_reduce_head_f32": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, cll, vp, cll, vp, vp, vp, vp, vp]),
     "iddgcn_head_dz_f32": (ci, [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp]),
     # include/iddgcn_graph.h
     "iddgcn_radix_sort_workspace": (cll, [cll, ci]),

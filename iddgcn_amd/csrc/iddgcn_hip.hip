@@ -3137,6 +3137,7 @@ __global__ __launch_bounds__(768) void sigma_tn_b3_kernel(long long M, int tiles
 }
 
 // out[D][R] partial of A^T dz and colsum(dz) per block; slab row layout [(D+1)][R]
+constexpr int TNN_G = 8;             // rows of A in flight per thread
 template <int D>
 __global__ __launch_bounds__(D) void gemm_tn_narrow_kernel(long long M, long long rows_per_block, int R,
                                                            const float* __restrict__ A,
@@ -3149,7 +3150,26 @@ __global__ __launch_bounds__(D) void gemm_tn_narrow_kernel(long long M, long lon
     const long long r_beg = (long long)blockIdx.x * rows_per_block;
     long long r_end = r_beg + rows_per_block;
     if (r_end > M) r_end = M;
-    for (long long e = r_beg; e < r_end; ++e) {
+    // whole groups of TNN_G rows: every row's a is loaded before the first is used (one row per iteration kept one
+    // load in flight per thread: 3x the stream time of A at config 3), then summed in row order, so each partial is
+    // bitwise the serial loop's; the ragged rest of the range runs the serial loop below
+    long long e = r_beg;
+    for (; e + TNN_G <= r_end; e += TNN_G) {
+        float a[TNN_G];
+#pragma unroll
+        for (int g = 0; g < TNN_G; ++g) a[g] = A[(e + g) * D + d];
+#pragma unroll
+        for (int g = 0; g < TNN_G; ++g) {
+#pragma unroll
+            for (int r = 0; r < MAX_R; ++r)
+                if (r < R) {
+                    const float z = dz[(e + g) * R + r];
+                    acc[r] += a[g] * z;
+                    accb[r] += z;
+                }
+        }
+    }
+    for (; e < r_end; ++e) {
         const float a = A[e * D + d];
 #pragma unroll
         for (int r = 0; r < MAX_R; ++r)
@@ -3870,15 +3890,40 @@ __global__ __launch_bounds__(256) void seg_gather_reduce_kernel(int n_nodes, con
 // SLOTS-th group of U edges (graphs with few nodes, e.g. the reference's 845, would otherwise
 // leave most of the chip idle behind a few long serial segments); the slot partials are summed
 // in fixed order (xor-shuffles) at the end, so results stay deterministic.
+// HEAD (round 12, iddgcn_tail_seg_reduce_head_f32: fp32 rows, R <= 2, D = 256, per-edge W): the semantics of
+// tail_seg_mfma8_kernel's HEAD form below.  The head chain's node terms of the same layer are added before the store,
+// dP[r][n] = fma(Wn[n][r], head_dO[n], tail sum) and dsum[n] = tail sum + head_dO[n]: the same two operands in the
+// same order as head_bwd_node_kernel's read-add-store (whose w * d + dP the compiler contracts to an fma), so dP and
+// dsum are bitwise what the unfused pair leaves.  dwh[n][r] = <head_dO[n], P_r[n]> comes from the pr[r] already in
+// registers.  head_dO[n] is loaded twice, for the dwh dots before the edge loop and again for the store: held across
+// the loop its 4 registers take the kernel past the 80-VGPR step to five waves per SIMD.
+// The head operands travel in the h_idx argument's place (HEAD has per-edge W, so no h_idx), so the non-HEAD
+// instantiations keep their kernel arguments and machine code.
 // ---------------------------------------------------------------------------
-template <int D, int R, bool BF = false>
+struct TailHeadArgs {
+    const float* head_dO;                   // (n_nodes, D) head seed of the layer
+    const float* Wn;                        // (n_nodes, R) node-level dynamic weights
+    float* dwh;                             // (n_nodes, R) out
+};
+template <bool HEAD>
+struct TailHeadSlot { typedef const int* __restrict__ type; };      // h_idx
+template <>
+struct TailHeadSlot<true> { typedef TailHeadArgs type; };           // W is per edge: no h_idx
+__device__ __forceinline__ const int* tail_h_idx(const int* p) { return p; }
+__device__ __forceinline__ const int* tail_h_idx(const TailHeadArgs&) { return nullptr; }
+__device__ __forceinline__ TailHeadArgs tail_head(const int*) { return TailHeadArgs{nullptr, nullptr, nullptr}; }
+__device__ __forceinline__ TailHeadArgs tail_head(const TailHeadArgs& a) { return a; }
+template <int D, int R, bool BF = false, bool HEAD = false>
 __global__ __launch_bounds__(256) void tail_seg_reduce_kernel(int n_nodes, const int* __restrict__ seg_ptr,
-                                                              const int* __restrict__ h_idx,
+                                                              const typename TailHeadSlot<HEAD>::type h_idx_or_head,
                                                               const float* __restrict__ W,
                                                               const float* __restrict__ dO,
                                                               const float* __restrict__ P, long long p_rel_stride,
                                                               float* __restrict__ dP, long long dp_rel_stride,
                                                               float* __restrict__ dsum, float* __restrict__ dWedge) {
+    const int* __restrict__ h_idx = tail_h_idx(h_idx_or_head);
+    const TailHeadArgs ha = tail_head(h_idx_or_head);
+    static_assert(!HEAD || (D == 256 && R <= 2 && !BF), "HEAD: one wave per node, fp32 rows, R <= 2");
     constexpr int LPR = D / 4;
     constexpr int SLOTS = 64 / LPR;                     // edge slots per node (one wave per node)
     constexpr int TS_U = 4;
@@ -3907,6 +3952,16 @@ __global__ __launch_bounds__(256) void tail_seg_reduce_kernel(int n_nodes, const
     for (int r = 0; r < R; ++r) {
         acc[r] = f32x4{0.f, 0.f, 0.f, 0.f};
         pr[r] = live ? ld4(P + r * p_rel_stride + n * D + sub * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    if constexpr (HEAD) {
+        // the node's own part of the dynamic-weight gradient (live is wave-uniform: one wave per node)
+        const f32x4 hd = live ? ld4(ha.head_dO + n * D + sub * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const f32x4 q = hd * pr[r];
+            const float tot = group_sum<LPR>(q[0] + q[1] + q[2] + q[3]);
+            if (live && sub == 0) ha.dwh[n * R + r] = tot;
+        }
     }
     f32x4 s4 = {0.f, 0.f, 0.f, 0.f};
     const int len = end - beg;
@@ -4038,6 +4093,16 @@ __global__ __launch_bounds__(256) void tail_seg_reduce_kernel(int n_nodes, const
         for (int q = 0; q < 4; ++q) s4[q] += __shfl_xor(s4[q], LPR * m, 64);
     }
     if (!live || slot != 0) return;
+    if constexpr (HEAD) {
+        const f32x4 hd = ld4(ha.head_dO + n * D + sub * 4);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const float wn = ha.Wn[n * R + r];
+            st4(dP + r * dp_rel_stride + n * D + sub * 4, fma4(f32x4{wn, wn, wn, wn}, hd, acc[r]));
+        }
+        if (dsum) st4(dsum + n * D + sub * 4, s4 + hd);
+        return;
+    }
 #pragma unroll
     for (int r = 0; r < R; ++r) st4(dP + r * dp_rel_stride + n * D + sub * 4, acc[r]);
     if (dsum) st4(dsum + n * D + sub * 4, s4);
@@ -4373,6 +4438,44 @@ __global__ __launch_bounds__(256) void head_dz_kernel(int n_nodes, int R, const 
     dot += __shfl_xor(dot, 2, 8);
     dot += __shfl_xor(dot, 4, 8);
     if (on) dz[n * R + r] = (dsv - dot) * sv;
+}
+// The same at R <= 2 (round 12, after iddgcn_tail_seg_reduce_head_f32; config 3: head segments of ~40 edges): the form
+// above would leave 6 of its 8 lanes idle behind a serial walk of the segment.  G lanes per node take every G-th
+// edge of the segment (as head_bwd_node_kernel's edge loop does) and their partials are summed by one butterfly, then
+// lane 0 of the group runs the softmax-sigmoid backward.  The sums associate differently from the form above and
+// from head_bwd_node_kernel (same terms): dz agrees with either in all but the last bits.
+template <int R, int G>
+__global__ __launch_bounds__(256) void head_dz_seg_kernel(int n_nodes, const float* __restrict__ Ssm,
+                                                          const float* __restrict__ W, const int* __restrict__ hptr,
+                                                          const int* __restrict__ hperm,
+                                                          const float* __restrict__ dWedge,
+                                                          const float* __restrict__ dwh, float* __restrict__ dz) {
+    const long long n = ((long long)blockIdx.x * blockDim.x + threadIdx.x) / G;
+    const int sub = threadIdx.x % G;
+    const bool live = n < n_nodes;
+    const int beg = live ? hptr[n] : 0, end = live ? hptr[n + 1] : 0;
+    float ep[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) ep[r] = 0.f;
+    for (int k = beg + sub; k < end; k += G) {
+        const float* dwe = dWedge + (long long)hperm[k] * R;
+#pragma unroll
+        for (int r = 0; r < R; ++r) ep[r] += dwe[r];
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) ep[r] = group_sum<G>(ep[r]);
+    if (!live || sub != 0) return;
+    float s[R], dsv[R];
+    float dot = 0.f;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const float w = W[n * R + r];
+        s[r] = Ssm[n * R + r];
+        dsv[r] = (dwh[n * R + r] + ep[r]) * w * (1.0f - w);
+        dot += dsv[r] * s[r];
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) dz[n * R + r] = (dsv[r] - dot) * s[r];
 }
 
 __global__ __launch_bounds__(256) void reduce_slabs_kernel(int n_slabs, long long n, const float* __restrict__ slab,
@@ -5772,11 +5875,37 @@ int iddgcn_tail_seg_reduce_head_bf16(void* stream, int n_nodes, int d, int R, co
     return launch_status();
 }
 
+int iddgcn_tail_seg_reduce_head_f32(void* stream, int n_nodes, int d, int R, const int* seg_ptr, const float* W,
+                                    const float* dO, const float* P, long long p_rel_stride, float* dP,
+                                    long long dp_rel_stride, float* dsum, float* dWedge, const float* head_dO,
+                                    const float* Wn, float* dwh) {
+    // the fp32 form exists for D = 256 at R <= 2 only (other shapes: the plain reduction + iddgcn_head_bwd_node_f32)
+    if (d != 256 || R < 1 || R > 2) return IDDGCN_E_BAD_ARG;
+    if (n_nodes < 0 || !seg_ptr || !W || !dO || !P || !dP || !dWedge || !head_dO || !Wn || !dwh)
+        return IDDGCN_E_BAD_ARG;
+    if (n_nodes == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned grid = grid_for(n_nodes, 64);       // one wave per node
+    const TailHeadArgs ha{head_dO, Wn, dwh};
+#define THK(RR) hipLaunchKernelGGL((tail_seg_reduce_kernel<256, RR, false, true>), dim3(grid), dim3(256), 0, st, n_nodes, seg_ptr, ha, W, dO, P, p_rel_stride, dP, dp_rel_stride, dsum, dWedge)
+    if (R == 1) THK(1);
+    else THK(2);
+#undef THK
+    return launch_status();
+}
+
 int iddgcn_head_dz_f32(void* stream, int n_nodes, int R, const float* Ssm, const float* W, const int* hseg_ptr,
                        const int* hperm, const float* dWedge, const float* dwh, float* dz) {
     if (R < 1 || R > MAX_R) return IDDGCN_E_BAD_REL;
     if (n_nodes < 0 || !Ssm || !W || !hseg_ptr || !hperm || !dWedge || !dwh || !dz) return IDDGCN_E_BAD_ARG;
     if (n_nodes == 0) return 0;
+    if (R <= 2) {                     // lane groups striding the segment
+        constexpr int G = 16;
+        const dim3 grid((unsigned)(((long long)n_nodes * G + 255) / 256));
+        if (R == 1) hipLaunchKernelGGL((head_dz_seg_kernel<1, G>), grid, dim3(256), 0, (hipStream_t)stream, n_nodes, Ssm, W, hseg_ptr, hperm, dWedge, dwh, dz);
+        else hipLaunchKernelGGL((head_dz_seg_kernel<2, G>), grid, dim3(256), 0, (hipStream_t)stream, n_nodes, Ssm, W, hseg_ptr, hperm, dWedge, dwh, dz);
+        return launch_status();
+    }
     hipLaunchKernelGGL(head_dz_kernel, dim3((unsigned)(((long long)n_nodes * 8 + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, n_nodes, R, Ssm, W, hseg_ptr, hperm, dWedge, dwh, dz);
     return launch_status();

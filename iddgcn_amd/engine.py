@@ -252,7 +252,7 @@ class Workspace:
         self.dAE = e(R, N, D)
         self.dES = e(N, D)
         self.dz = e(N, R)
-        self.dwh = e(N, R)                      # <head seed, P_r> per node (fused R = 8 tail + head backward)
+        self.dwh = e(N, R)                      # <head seed, P_r> per node (fused tail + head backward)
         self.WaT = e(R, D)
         self.drel_slab = e(self.nb_dm * R * D)
         self.loss_slab = e(self.nb_dm)
@@ -304,8 +304,9 @@ class Engine:
             raise L.IddgcnError("edge_mfma='bf16' needs features='bf16' (bf16 edge tables)")
         self.edge_mfma = edge_mfma
         self.fuse_sigma_tn = True
-        # bf16 edge tables at R = 8, D = 256: the tail reduction adds the head chain's node terms (tail_seg_reduce_head)
-        # and head_dz finishes the head side; False runs the plain tail reduction + head_bwd_node (A/B, tests)
+        # bf16 edge tables at R = 8, D = 256 and fp32 edge tables at R <= 2, D = 256 (the headline): the tail reduction
+        # adds the head chain's node terms (tail_seg_reduce_head) and head_dz finishes the head side; False runs the
+        # plain tail reduction + head_bwd_node (A/B, tests)
         self.fuse_tail_head = True
         if not 1 <= num_relations <= 8:
             raise L.IddgcnError("num_relations must be in [1, 8]")
@@ -555,9 +556,11 @@ class Engine:
             # first waits for everything queued so far (the previous layer's readers of dP), and the
             # main stream waits for it before the head-side work that reads dP, dWedge
             side = self._side_stream() if (self.overlap and l > 0) else None
-            # bf16 edge tables at R = 8, D = 256 (config 5): the tail reduction on MFMAs adds the head chain's node terms
-            # (Wl[n] dO[n] into dP, dO[n] into dES) before its store, so the head backward below skips them
-            fused = self.fuse_tail_head and self.features == "bf16" and R == 8 and D == 256 and self.node_shard is None
+            # bf16 edge tables at R = 8, D = 256 (config 5, on MFMAs) and fp32 edge tables at R <= 2, D = 256 (configs
+            # 3 / 4): the tail reduction adds the head chain's node terms (Wl[n] dO[n] into dP, dO[n] into dES) before
+            # its store, so the head backward below skips them (fp32: dP and dES bitwise the unfused pair's)
+            fused = (self.fuse_tail_head and D == 256 and self.node_shard is None and
+                     ((self.features == "bf16" and R == 8) or (self.features == "f32" and R <= 2)))
             if side is not None:
                 side.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(side):

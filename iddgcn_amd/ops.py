@@ -404,10 +404,12 @@ def _req_rel_rows(t, shape, name):
 
 
 def tail_seg_reduce_head(seg_ptr, W, dO, P, dP, dWedge, head_dO, Wn, dwh, dsum=None):
-    """tail_seg_reduce with per-edge W on bf16 rows at R = 8, D = 256, fused with the head chain's node terms of the
-    same layer (iddgcn_tail_seg_reduce_head_bf16, ABI 9): dP[r][n] = tail sum + Wn[n][r] head_dO[n], dsum[n] = tail
-    sum + head_dO[n], dwh[n][r] = <head_dO[n], P_r[n]>; the head backward is then head_dz.  P, dP: (R, n, D) views
-    with contiguous rows (a node-row range: seg_ptr the matching slice of the tail pointers, absolute edge offsets)."""
+    """tail_seg_reduce with per-edge W fused with the head chain's node terms of the same layer: dP[r][n] = tail sum
+    + Wn[n][r] head_dO[n], dsum[n] = tail sum + head_dO[n], dwh[n][r] = <head_dO[n], P_r[n]>; the head backward is
+    then head_dz.  bf16 rows at R = 8, D = 256 (iddgcn_tail_seg_reduce_head_bf16, ABI 9) or fp32 rows at R <= 2,
+    D = 256 (iddgcn_tail_seg_reduce_head_f32, round 12: dP, dsum bitwise tail_seg_reduce + head_bwd_node), by the dtype
+    of dO; other shapes are refused.  P, dP: (R, n, D) views with contiguous rows (a node-row range: seg_ptr the
+    matching slice of the tail pointers, absolute edge offsets)."""
     R, n_nodes, D = P.shape
     _req(seg_ptr, _I32, (n_nodes + 1,), "seg_ptr")
     ps = _req_rel_rows(P, (R, n_nodes, D), "P")
@@ -416,13 +418,15 @@ def tail_seg_reduce_head(seg_ptr, W, dO, P, dP, dWedge, head_dO, Wn, dwh, dsum=N
     _req(head_dO, _F32, (n_nodes, D), "head_dO")
     _req(Wn, _F32, (n_nodes, R), "Wn")
     _req(dwh, _F32, (n_nodes, R), "dwh")
-    _req(dO, _BF16, None, "dO")
+    bf = dO.dtype == _BF16
+    _req(dO, _BF16 if bf else _F32, None, "dO")
+    _req(W, _F32, None, "W")
+    _req(dWedge, _F32, None, "dWedge")
     if W.shape[0] != dO.shape[0]:
         raise L.IddgcnError("tail_seg_reduce_head: per-edge W must have one row per edge")
-    L.check(L.lib().iddgcn_tail_seg_reduce_head_bf16(_stream(), n_nodes, D, R, _ptr(seg_ptr), _ptr(W), _ptr(dO),
-                                                     _ptr(P), ps, _ptr(dP), dps, _ptr(dsum),
-                                                     _ptr(dWedge), _ptr(head_dO), _ptr(Wn), _ptr(dwh)),
-            "tail_seg_reduce_head")
+    fn = L.lib().iddgcn_tail_seg_reduce_head_bf16 if bf else L.lib().iddgcn_tail_seg_reduce_head_f32
+    L.check(fn(_stream(), n_nodes, D, R, _ptr(seg_ptr), _ptr(W), _ptr(dO), _ptr(P), ps, _ptr(dP), dps, _ptr(dsum),
+               _ptr(dWedge), _ptr(head_dO), _ptr(Wn), _ptr(dwh)), "tail_seg_reduce_head")
 
 
 def head_dz(Ssm, W, hseg_ptr, hperm, dWedge, dwh, dz):

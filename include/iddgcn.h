@@ -378,9 +378,22 @@ int iddgcn_tail_seg_reduce_head_bf16(void* stream, int n_nodes, int d, int R, co
                                      long long dp_rel_stride, float* dsum, float* dWedge, const float* head_dO,
                                      const float* Wn, float* dwh);
 
-/* ABI 9: the rest of iddgcn_head_bwd_node_f32 after iddgcn_tail_seg_reduce_head_bf16, node n:
+/* Round 12 (added symbol only, the ABI version stays 13): the same fusion over fp32 edge rows, for d = 256 and R <= 2
+ * only (any other shape: IDDGCN_E_BAD_ARG; use iddgcn_tail_seg_reduce_f32 + iddgcn_head_bwd_node_f32).  W is per edge
+ * (W[e][r], iddgcn_gather_rows_f32).  dP and dsum are bitwise what iddgcn_tail_seg_reduce_f32 followed by
+ * iddgcn_head_bwd_node_f32 leaves (the head term enters by the same single fma / add), dWedge bitwise
+ * iddgcn_tail_seg_reduce_f32's; every node stores its rows, also a node without edges.  The head backward is then
+ * iddgcn_head_dz_f32. */
+int iddgcn_tail_seg_reduce_head_f32(void* stream, int n_nodes, int d, int R, const int* seg_ptr, const float* W,
+                                    const float* dO, const float* P, long long p_rel_stride, float* dP,
+                                    long long dp_rel_stride, float* dsum, float* dWedge, const float* head_dO,
+                                    const float* Wn, float* dwh);
+
+/* ABI 9: the rest of iddgcn_head_bwd_node_f32 after iddgcn_tail_seg_reduce_head_bf16 / _f32, node n:
  *   dW_r = dwh[n][r] + sum_{k in hseg(n)} dWedge[hperm[k]][r];  ds_r = dW_r w_r (1-w_r);
- *   dz[n][j] = s_j (ds_j - sum_r ds_r s_r)                                  (W = Wn, s = Ssm; n_nodes x R each) */
+ *   dz[n][j] = s_j (ds_j - sum_r ds_r s_r)                                  (W = Wn, s = Ssm; n_nodes x R each)
+ * R <= 2 (round 12): 16 lanes per node stride the head segment and reduce once (R > 2: one lane per relation walks it
+ * in order); the order of the dW sum is not part of the contract. */
 int iddgcn_head_dz_f32(void* stream, int n_nodes, int R, const float* Ssm, const float* W, const int* hseg_ptr,
                        const int* hperm, const float* dWedge, const float* dwh, float* dz);
 
