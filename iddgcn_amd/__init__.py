@@ -15,3 +15,6 @@ from .utils import generate_reverse_triplets, get_y_true  # noqa: F401
 from .metrics import classification_metrics, ranking_metrics  # noqa: F401
 from . import explain  # noqa: F401,E402  (explaiNE / GNNExplainer / IDDGCN explainer on the HIP path)
 from . import similarity  # noqa: F401,E402  (feat_similarity.py similarity graph on MFMA)
+from . import ground_truth  # noqa: F401,E402  (explanation ground truth on the GPU, P/R/F1@k of the explainers)
+from .ground_truth import (construct_ground_truth, evaluate_explanations, filter_ground_truth,  # noqa: F401,E402
+                           ground_truth_table, load_similarity_csv)

@@ -1,5 +1,5 @@
 """ctypes binding of libiddgcn_hip.so (C-ABI declared in include/iddgcn.h, iddgcn_graph.h,
-iddgcn_similarity.h, iddgcn_sampling.h, iddgcn_screen.h and iddgcn_explain.h).
+iddgcn_similarity.h, iddgcn_sampling.h, iddgcn_screen.h, iddgcn_explain.h and iddgcn_ground_truth.h).
 
 The product path has no CPU fallback: if the shared library is missing, was
 built for another ABI version or from other sources than the tree beside it
@@ -143,7 +143,16 @@ SIGNATURES = {
     "iddgcn_explain_topk_f32": (ci, [vp, ci, ci, vp, vp, vp, vp, vp, vp]),
     # batched mask explainers (added symbol only)
     "iddgcn_mask_explain_f32": (ci, [vp, ctypes.POINTER(MaskExplainArgs)]),
+    # include/iddgcn_ground_truth.h (explanation ground truth; added symbols only)
+    "iddgcn_gt_sim_lists_workspace": (ci, [cll, ctypes.POINTER(cll)]),
+    "iddgcn_gt_sim_lists": (ci, [vp, cll, ci, vp, vp, vp, vp, vp, vp, cll]),
+    "iddgcn_gt_dc_table_workspace": (ci, [cll, ci, ci, ctypes.POINTER(cll)]),
+    "iddgcn_gt_dc_table": (ci, [vp, cll, ci, ci, vp, vp, vp, vp, vp, cll]),
+    "iddgcn_ground_truth_count": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "iddgcn_gt_exclusive_scan": (ci, [vp, ci, vp, vp]),
+    "iddgcn_ground_truth_fill": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp]),
 }
+GT_LIST_CAPACITY = 8192      # IDDGCN_GT_LIST_CAPACITY
 
 _lib = None
 

@@ -1009,3 +1009,86 @@ def mask_explain(E, K, S, Wa, ba, rel, h, r, t, qptr, entry, crel, ccol, crole, 
         a.n_queries = hi - lo
         L.check(fn(st, ctypes.byref(a)), "mask_explain")
     return out
+
+
+# -- explanation ground truth (include/iddgcn_ground_truth.h) ------------------------------------
+def _triples3(t, name):
+    _req(t, _I64, None, name)
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise L.IddgcnError(f"{name} must be (n, 3), got {tuple(t.shape)}")
+
+
+def gt_sim_lists(sim, N):
+    """Similarity lists of every node as a CSR (ptr [N+1], val [2n], first [2n]) and the device error flag (not
+    read here).  sim: (n, 3) int64 GPU tensor."""
+    _triples3(sim, "sim")
+    n, dev = sim.shape[0], sim.device
+    need = ctypes.c_longlong(0)
+    L.check(L.lib().iddgcn_gt_sim_lists_workspace(n, ctypes.byref(need)), "gt_sim_lists_workspace")
+    ws = _workspace(need.value, dev)
+    ptr = torch.empty(N + 1, dtype=_I32, device=dev)
+    val = torch.empty(max(2 * n, 1), dtype=_I32, device=dev)
+    first = torch.empty(max(2 * n, 1), dtype=_U8, device=dev)
+    err = torch.empty(1, dtype=_I32, device=dev)
+    L.check(L.lib().iddgcn_gt_sim_lists(_stream(), n, N, _ptr(sim), _ptr(ptr), _ptr(val), _ptr(first), _ptr(err),
+                                        _ptr(ws), ws.numel()), "gt_sim_lists")
+    return ptr, val, first, err
+
+
+def gt_dc_table(dc, N, R):
+    """dc as a CSR over (rel, drug) of the sorted mutations (seg_ptr [R*N+1], seg_mu [M]) and the device error
+    flag (not read here).  dc: (M, 3) int64 GPU tensor."""
+    _triples3(dc, "dc")
+    M, dev = dc.shape[0], dc.device
+    need = ctypes.c_longlong(0)
+    L.check(L.lib().iddgcn_gt_dc_table_workspace(M, N, R, ctypes.byref(need)), "gt_dc_table_workspace")
+    ws = _workspace(need.value, dev)
+    seg_ptr = torch.empty(R * N + 1, dtype=_I32, device=dev)
+    seg_mu = torch.empty(max(M, 1), dtype=_I32, device=dev)
+    err = torch.empty(1, dtype=_I32, device=dev)
+    L.check(L.lib().iddgcn_gt_dc_table(_stream(), M, N, R, _ptr(dc), _ptr(seg_ptr), _ptr(seg_mu), _ptr(err), _ptr(ws),
+                                       ws.numel()), "gt_dc_table")
+    return seg_ptr, seg_mu, err
+
+
+def _gt_tables(mu, drug, dc, N, R):
+    (mp, mv, mf), (dp, dv, df), (sp, sm) = mu, drug, dc
+    for p, v, f, nm in ((mp, mv, mf, "mu"), (dp, dv, df, "drug")):
+        _req(p, _I32, (N + 1,), nm + " ptr")
+        _req(v, _I32, None, nm + " val")
+        _req(f, _U8, (v.shape[0],), nm + " first")
+    _req(sp, _I32, (R * N + 1,), "seg_ptr")
+    _req(sm, _I32, None, "seg_mu")
+    return [_ptr(x) for x in (mp, mv, mf, dp, dv, df, sp, sm)]
+
+
+def ground_truth_count(queries, mu, drug, dc, N, R):
+    """COUNT pass: (len [Q] int64, err [1] int32), both on the device.  The queries' ids must be in range (the
+    caller checks: ground_truth.construct_ground_truth)."""
+    _triples3(queries, "queries")
+    Q, dev = queries.shape[0], queries.device
+    length = torch.empty(max(Q, 1), dtype=_I64, device=dev)
+    err = torch.zeros(1, dtype=_I32, device=dev)
+    L.check(L.lib().iddgcn_ground_truth_count(_stream(), Q, N, R, _ptr(queries), *_gt_tables(mu, drug, dc, N, R),
+                                              _ptr(length), _ptr(err)), "ground_truth_count")
+    return length[:Q], err
+
+
+def gt_exclusive_scan(length):
+    _req(length, _I64, None, "len")
+    Q = length.shape[0]
+    ptr = torch.empty(Q + 1, dtype=_I64, device=length.device)
+    L.check(L.lib().iddgcn_gt_exclusive_scan(_stream(), Q, _ptr(length) if Q else None, _ptr(ptr)),
+            "gt_exclusive_scan")
+    return ptr
+
+
+def ground_truth_fill(queries, mu, drug, dc, N, R, ptr, total, drug_rel, mu_rel):
+    """FILL pass: the (total, 3) int64 triples, query q's at rows ptr[q] .. ptr[q+1]."""
+    _triples3(queries, "queries")
+    Q = queries.shape[0]
+    _req(ptr, _I64, (Q + 1,), "ptr")
+    out = torch.empty((max(int(total), 1), 3), dtype=_I64, device=queries.device)
+    L.check(L.lib().iddgcn_ground_truth_fill(_stream(), Q, N, R, _ptr(queries), *_gt_tables(mu, drug, dc, N, R),
+                                             _ptr(ptr), int(drug_rel), int(mu_rel), _ptr(out)), "ground_truth_fill")
+    return out[:int(total)]
