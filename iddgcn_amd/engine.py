@@ -448,85 +448,153 @@ class Engine:
     # all-gathered, dAE reduce-scattered to the row owners before a transposed SpMM over their columns
     spmm_shard = None
 
+    # The step's stages.  Every kernel launch of the step is written once, in one of the small methods below; forward,
+    # backward, their node-partitioned forms, _node_tables and _screen_layered are sequences of them.  ``rows`` is
+    # None for whole node tables (the tensors themselves, no view built) or the (a, b) of a node-partitioned step.
+    @staticmethod
+    def _rows(t, rows, dim=0):
+        if rows is None:
+            return t
+        return t[rows[0]:rows[1]] if dim == 0 else t[:, rows[0]:rows[1]]
+
+    def _require_unsharded(self, what):
+        if self.node_shard is not None or self.spmm_shard is not None or self.row_shard is not None:
+            raise L.IddgcnError(f"{what}: not available on an Engine with node_shard / spmm_shard / row_shard set")
+
+    def _triples(self, triples, name, one):
+        """(Q, 3) (h, r, t) as a checked int64 host array; the messages call the array ``name`` and a row ``one``."""
+        q = np.asarray(triples.cpu() if isinstance(triples, torch.Tensor) else triples).astype(np.int64)
+        if q.ndim != 2 or q.shape[1] != 3:
+            raise L.IddgcnError(f"{name} must be (Q, 3), got {q.shape}")
+        if len(q) and (min(q[:, 0].min(), q[:, 2].min()) < 0 or max(q[:, 0].max(), q[:, 2].max()) >= self.N):
+            raise L.IddgcnError(f"{one} entity index out of range [0, num_entities)")
+        if len(q) and (q[:, 1].min() < 0 or q[:, 1].max() >= self.R):
+            raise L.IddgcnError(f"{one} relation index out of range [0, num_relations)")
+        return q
+
+    def _ae(self, adj, E, ws, r=None, n0=0, n1=0):
+        """AE_r = A_r·E (IDDGCN.py:69-70): all relations in one launch, or the rows [n0, n1) of relation r."""
+        if r is None:
+            return ops.spmm_csr(adj.fwd_ptr, adj.fwd_col, adj.fwd_val, E, ws.AE, self.R, self.N)
+        p0 = r * (self.N + 1)
+        ops.spmm_csr(adj.fwd_ptr[p0 + n0:p0 + n1 + 1], adj.fwd_col, adj.fwd_val, E,
+                     ws.AE[r][n0:n1].view(1, n1 - n0, self.D), 1, n1 - n0)
+
+    def _projections(self, P, ws, rows=None):
+        """P_r^l = AE_r·K_r^l of the node rows (node-level form of IDDGCN.py:71-72,76-77), every layer and relation:
+        independent GEMMs, for _rowgemm_batches."""
+        pn = dict(precision=self.proj_gemm)
+        return [(self._rows(ws.AE[r], rows), P[f"K{l + 1}"][r], self._rows(ws.P[l, r], rows), pn)
+                for l in range(NUM_LAYERS) for r in range(self.R)]
+
+    def _es1(self, P, ws, rows=None):
+        """E·S^1, layer 1's x·S at node level for both sides (inputs E[h], E[t]), as (A, B, C, kwargs) of a row GEMM."""
+        return self._rows(P["E"], rows), P["S1"], self._rows(ws.ES1, rows), dict(precision=self.proj_gemm)
+
+    def _rowgemm_batches(self, proj):
+        """The independent node-level projections ``proj``, L.ROWGEMM_BATCH per launch (one launch below D=256)."""
+        for i in range(0, len(proj), L.ROWGEMM_BATCH):
+            ops.rowgemm_batched(proj[i:i + L.ROWGEMM_BATCH])
+
+    def _alpha(self, P, ws, l, rows=None):
+        """The dynamic weights W^l (and their softmax) of the node rows, from the layer's head input (IDDGCN.py:66)."""
+        X = self._rows(ws.X[l - 1] if l else P["E"], rows)
+        ops.alpha_fwd(X, P[f"Wa{l + 1}"], P[f"ba{l + 1}"], self._rows(ws.Ssm[l], rows), self._rows(ws.W[l], rows))
+
+    @property
+    def _head_via_scratch(self):
+        """Head-chain layers 2-3 as a plain GEMM into a scratch table + the row-aligned combine, not the fused GEMM."""
+        return self.R > 2 and self.D == 256
+
+    def _head_layer(self, P, ws, l, scratch, rows=None, idx=None):
+        """X^{l+1} of the node rows from ES1 (layer 1) or X^l (layers 2, 3), W and P of the layer.  ``idx``: the rows'
+        numbers, where the tables are read through a range; ``scratch``: a free N x D table for X^l·S at many
+        relations (None: the caller has none, the fused GEMM runs)."""
+        W, Xout = self._rows(ws.W[l], rows), self._rows(ws.X[l], rows)
+        if l == 0:
+            return ops.combine(ws.ES1, W, ws.P[0], Xout, y_idx=idx, v_idx=idx)
+        Xin, S, pr = self._rows(ws.X[l - 1], rows), P[f"S{l + 1}"], self.row_gemm
+        if self._head_via_scratch and scratch is not None:
+            # sigma(Y + sum_r W_r P_r) row-aligned — every node row's own 8 V rows, which the fused GEMM's gathered-V
+            # epilogue (built for tail runs) stages through its capped slabs one row at a time: config 5 4.5 ms ->
+            # 0.6 + 1.9 ms
+            tmp = self._rows(scratch, rows)
+            ops.rowgemm(Xin, S, tmp, precision=pr)
+            ops.combine(tmp, W, ws.P[l], Xout, v_idx=idx)
+        else:
+            ops.rowgemm(Xin, S, Xout, coef=W, V=ws.P[l], v_idx=idx, v_rel_stride=self.N * self.D, act=L.ACT_SIGMOID,
+                        precision=pr)
+
+    def _gather_w(self, ws, l, h, we):
+        """W^l[h_e]: the per-edge copy of the dynamic weights."""
+        ops.gather_rows(ws.W[l], h, we[l])
+
+    def _tail_layer(self, P, ws, l, t, xt, we):
+        """x^{l+1} of the scored edges: layer 1 a gather-combine of node tables (ES1 must still hold E·S^1), layers 2-3
+        x^l·S fused with the gather of P[t] scaled by W[h]."""
+        pl = self.use_planes
+        if l == 0:
+            return ops.combine(ws.ES1, we[0], ws.P[0], xt[0], y_idx=t, v_idx=t, planes_out=pl)
+        with self._mark("tail_fwd_gemm"):
+            ops.rowgemm(xt[l - 1], P[f"S{l + 1}"], xt[l], coef=we[l], V=ws.P[l], v_idx=t, v_rel_stride=self.N * self.D,
+                        act=L.ACT_SIGMOID, planes=(L.PLANES_A | (L.PLANES_C if l == 1 else 0)) if pl else 0,
+                        precision=self.edge_gemm)
+
+    def _dm_seed(self, T):
+        if self._pred_seed is None:        # Keras BCE, x 1/num_entities (IDDGCN.py:161-168)
+            return 1.0 / (float(self._t_global or T) * float(self.N)), True
+        return float(self._pred_seed), False   # d(scale * sum_e p_e): the explainers' seed
+
+    def _distmult_scores(self, P, ws, h, r, x3, p_out, s_out):
+        ops.distmult_bce(ws.X[2], h, x3, r, P["rel"], p_out=p_out, s_out=s_out)
+
+    def _distmult(self, P, ed, ws, train):
+        """DistMult (+ BCE and the backward seeds when training)."""
+        if not train:
+            return self._distmult_scores(P, ws, ed.h, ed.r, ws.xt[2], ws.p, ws.s)
+        # one pass over head segments: p / loss / drel partials, the tail seed do^3 (per edge, written over x^3 in
+        # place: each edge row is read, then written, by the same lanes) and the head seed dO^3[n] = X3(1-X3) *
+        # sum_{h_e=n} ds_e rel[r_e] * x3_e
+        scale, bce = self._dm_seed(ed.T)
+        ops.distmult_bce_heads(ed.hptr, ed.hperm, ws.X[2], ws.xt[2], ed.r, P["rel"], ed.y if bce else None, ws.xt[2],
+                               ws.dOn_a, ws.drel_slab, ws.loss_slab, scale=scale,
+                               p_out=ws.p if self._want_p else None, s_out=ws.s if self._want_p else None)
+
     def forward(self, P, adj, ed, ws, train):
         if self.row_shard is not None:
             return self._forward_rows(P, adj, ed, ws, train)
-        N, R, D, T = self.N, self.R, self.D, ed.T
+        N, R, D = self.N, self.R, self.D
         E = P["E"]
-        # NOTE: _node_tables (all-candidate ranking) repeats the node-level launches of the unsharded path below —
-        # AE, P, ES1, W^l, X^l — and must follow any change to them (tests/test_gpu_ranking.py compares its tables
-        # with this forward's bitwise).
-        # every GEMM call carries this engine's operand precision: pn for the plain node-level projections, pr for
-        # the other row GEMMs
-        pn = dict(precision=self.proj_gemm)
-        pr = dict(precision=self.row_gemm)      # (the other row GEMMs)
-        sh = self.node_shard
-        if sh is None and self.spmm_shard is not None:
-            # row-partitioned A_r·E (every rank holds E): this rank's (relation, row) pieces, then all-gather
-            ss = self.spmm_shard
-            for r, n0, n1 in ss.pieces():
-                ops.spmm_csr(adj.fwd_ptr[r * (N + 1) + n0:r * (N + 1) + n1 + 1], adj.fwd_col, adj.fwd_val, E,
-                             ws.AE[r][n0:n1].view(1, n1 - n0, D), 1, n1 - n0)
-            ss.all_gather(ws.AE.view(R * N, D))
-            proj = [(ws.AE[r], P[f"K{l + 1}"][r], ws.P[l, r], pn) for l in range(NUM_LAYERS) for r in range(R)]
-        elif sh is None:
-            # AE_r = A_r·E, all relations in one launch (IDDGCN.py:69-70)
-            ops.spmm_csr(adj.fwd_ptr, adj.fwd_col, adj.fwd_val, E, ws.AE, R, N)
-            # P_r^l = AE_r·K_r^l (node-level form of IDDGCN.py:71-72,76-77) and, layer 1, x·S1 at node
-            # level for both sides (inputs E[h], E[t]): independent GEMMs, batched (one launch below D=256)
-            proj = [(ws.AE[r], P[f"K{l + 1}"][r], ws.P[l, r], pn) for l in range(NUM_LAYERS) for r in range(R)]
-        else:
+        sh, ss = self.node_shard, self.spmm_shard
+        if sh is not None:
             # relation-sharded: this rank's (relation, node-row) pieces of AE_r and P_r^l, then all-gather P
+            pn = dict(precision=self.proj_gemm)
             proj = []
             for r, n0, n1 in sh.pieces():
-                ops.spmm_csr(adj.fwd_ptr[r * (N + 1) + n0:r * (N + 1) + n1 + 1], adj.fwd_col, adj.fwd_val, E,
-                             ws.AE[r][n0:n1].view(1, n1 - n0, D), 1, n1 - n0)
+                self._ae(adj, E, ws, r, n0, n1)
                 proj += [(ws.AE[r][n0:n1], P[f"K{l + 1}"][r], ws.P[l, r][n0:n1], pn) for l in range(NUM_LAYERS)]
-        proj.append((E, P["S1"], ws.ES1, pn))
-        nb = L.ROWGEMM_BATCH
-        for i in range(0, len(proj), nb):
-            ops.rowgemm_batched(proj[i:i + nb])
+        else:
+            if ss is not None:
+                # row-partitioned A_r·E (every rank holds E): this rank's (relation, row) pieces, then all-gather
+                for r, n0, n1 in ss.pieces():
+                    self._ae(adj, E, ws, r, n0, n1)
+                ss.all_gather(ws.AE.view(R * N, D))
+            else:
+                self._ae(adj, E, ws)
+            proj = self._projections(P, ws)
+        proj.append(self._es1(P, ws))
+        self._rowgemm_batches(proj)
         if sh is not None:
             for l in range(NUM_LAYERS):
                 sh.all_gather(ws.P[l].view(R * N, D))
-        ops.alpha_fwd(E, P["Wa1"], P["ba1"], ws.Ssm[0], ws.W[0])
-        ops.gather_rows(ws.W[0], ed.h, ws.Wedge[0])
-        ops.combine(ws.ES1, ws.W[0], ws.P[0], ws.X[0])
-        pl = self.use_planes
-        ops.combine(ws.ES1, ws.Wedge[0], ws.P[0], ws.xt[0], y_idx=ed.t, v_idx=ed.t, planes_out=pl)
-        # layers 2, 3
-        for l in (1, 2):
-            S = P[f"S{l + 1}"]
-            ops.alpha_fwd(ws.X[l - 1], P[f"Wa{l + 1}"], P[f"ba{l + 1}"], ws.Ssm[l], ws.W[l])
-            ops.gather_rows(ws.W[l], ed.h, ws.Wedge[l])
-            if R > 2 and D == 256:
-                # head chain at node level, many relations: X^{l-1}·S into ES1 (free once the layer-1 combines above
-                # have read it), then the row-aligned combine sigma(Y + sum_r W_r P_r) — every node row's own 8 V rows,
-                # which the fused GEMM's gathered-V epilogue (built for tail runs) stages through its capped slabs
-                # one row at a time: config 5 4.5 ms -> 0.6 + 1.9 ms
-                ops.rowgemm(ws.X[l - 1], S, ws.ES1, **pr)
-                ops.combine(ws.ES1, ws.W[l], ws.P[l], ws.X[l])
-            else:
-                ops.rowgemm(ws.X[l - 1], S, ws.X[l], coef=ws.W[l], V=ws.P[l], v_rel_stride=N * D,
-                            act=L.ACT_SIGMOID, **pr)
-            with self._mark("tail_fwd_gemm"):
-                ops.rowgemm(ws.xt[l - 1], S, ws.xt[l], coef=ws.Wedge[l], V=ws.P[l], v_idx=ed.t,
-                            v_rel_stride=N * D, act=L.ACT_SIGMOID,
-                            planes=(L.PLANES_A | (L.PLANES_C if l == 1 else 0)) if pl else 0, precision=self.edge_gemm)
-        # DistMult (+ BCE and backward seed when training)
-        if train:
-            # one pass over head segments: p / loss / drel partials, the tail seed do^3 (per edge)
-            # and the head seed dO^3[n] = X3(1-X3) * sum_{h_e=n} ds_e rel[r_e] * x3_e
-            if self._pred_seed is None:        # Keras BCE, x 1/num_entities (IDDGCN.py:161-168)
-                scale, y = 1.0 / (float(self._t_global or T) * float(N)), ed.y
-            else:                              # d(scale * sum_e p_e): the explainers' seed
-                scale, y = float(self._pred_seed), None
-            # do^3 is written over x^3 in place (each edge row is read, then written, by the same lanes)
-            ops.distmult_bce_heads(ed.hptr, ed.hperm, ws.X[2], ws.xt[2], ed.r, P["rel"], y, ws.xt[2], ws.dOn_a,
-                                   ws.drel_slab, ws.loss_slab, scale=scale, p_out=ws.p if self._want_p else None,
-                                   s_out=ws.s if self._want_p else None)
-        else:
-            ops.distmult_bce(ws.X[2], ed.h, ws.xt[2], ed.r, P["rel"], p_out=ws.p, s_out=ws.s)
+        # head and tail side interleaved layer by layer; at many relations the head chain's X^{l-1}·S goes through ES1,
+        # free once the layer-1 combines have read it
+        for l in range(NUM_LAYERS):
+            self._alpha(P, ws, l)
+            self._gather_w(ws, l, ed.h, ws.Wedge)
+            self._head_layer(P, ws, l, ws.ES1)
+            self._tail_layer(P, ws, l, ed.t, ws.xt, ws.Wedge)
+        self._distmult(P, ed, ws, train)
 
     _t_global = None
     _want_p = False        # per-edge probabilities are only materialised for loss_and_grads
@@ -542,115 +610,146 @@ class Engine:
         if self.row_shard is not None:
             return self._backward_rows(P, G, adj, ed, ws, comm, e_owner)
         N, R, D = self.N, self.R, self.D
-        pk, pn, pr = dict(precision=self.gemm), dict(precision=self.proj_gemm), dict(precision=self.row_gemm)
         dOn, dOn_next = ws.dOn_a, ws.dOn_b      # head seed dO^3, written by distmult_bce_heads
-        if self.node_shard is not None:
+        sh = self.node_shard
+        if sh is not None:
             ws.dAE.zero_()                      # rows other ranks own stay 0 in the dE SpMM below
-        pl = self.use_planes                    # x^1, x^2 are planes tables (forward)
         for l in (2, 1, 0):                     # layer index l -> reference layer l+1
-            Wl, Pl, Sl = ws.W[l], ws.P[l], P[f"S{l + 1}"]
-            do = ws.xt[l]                       # do^{l+1}, written over x^{l+1}
-            # tail side: dP (tail part), dWedge, and for layer 1 the dES tail part.  With `overlap` (layers
-            # 2-3) the HBM-bound reduction runs on a side stream beside the MFMA-bound dS TN and sigma'
-            # GEMM (it reads do, P, Wedge and writes dP, dWedge: nothing those two touch); the side stream
-            # first waits for everything queued so far (the previous layer's readers of dP), and the
-            # main stream waits for it before the head-side work that reads dP, dWedge
-            side = self._side_stream() if (self.overlap and l > 0) else None
-            # bf16 edge tables at R = 8, D = 256 (config 5, on MFMAs) and fp32 edge tables at R <= 2, D = 256 (configs
-            # 3 / 4): the tail reduction adds the head chain's node terms (Wl[n] dO[n] into dP, dO[n] into dES) before
-            # its store, so the head backward below skips them (fp32: dP and dES bitwise the unfused pair's)
-            fused = (self.fuse_tail_head and D == 256 and self.node_shard is None and
-                     ((self.features == "bf16" and R == 8) or (self.features == "f32" and R <= 2)))
-            if side is not None:
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    if fused:
-                        ops.tail_seg_reduce_head(ed.tptr, ws.Wedge[l], do, Pl, ws.dP, ws.dWedge, dOn, Wl, ws.dwh)
-                    else:
-                        ops.tail_seg_reduce(ed.tptr, None, ws.Wedge[l], do, Pl, ws.dP, ws.dWedge)
-            elif fused:
-                ops.tail_seg_reduce_head(ed.tptr, ws.Wedge[l], do, Pl, ws.dP, ws.dWedge, dOn, Wl, ws.dwh,
-                                         dsum=ws.dES if l == 0 else None)
-            else:
-                ops.tail_seg_reduce(ed.tptr, None, ws.Wedge[l], do, Pl, ws.dP, ws.dWedge,
-                                    dsum=ws.dES if l == 0 else None)
-            if l > 0 and self.sigma_tn_fused:
-                with self._mark("tail_bwd_sigma_tn"):
-                    ops.sigma_tn(do, ws.xt[l - 1], Sl, G[f"S{l + 1}"], ws.tn_slab, precision=self.edge_gemm)
-            elif l > 0:
-                # dS^{l+1} (edge part) = x_t^{l}^T do ; do^{l} = (do S^T) * x(1-x), written over x^{l}
-                with self._mark("tail_dS_tn"):
-                    ops.gemm_tn(ws.xt[l - 1], do, G[f"S{l + 1}"], ws.tn_slab, a_planes=pl, **pk)
-                with self._mark("tail_bwd_gemm"):
-                    ops.rowgemm(do, Sl, ws.xt[l - 1], b_trans=True, act=L.ACT_DSIGMOID, aux=ws.xt[l - 1],
-                                planes=L.PLANES_AUX if pl else 0, precision=self.edge_gemm)
-            if side is not None:
-                torch.cuda.current_stream().wait_stream(side)
+            Wl, Pl = ws.W[l], ws.P[l]
+            fused = self._tail_head_fused(l)
+            self._tail_bwd(P, G, ws, l, ed.tptr, dOn, Wl, Pl, fused)
             # head side (node level)
             if fused:
                 ops.head_dz(ws.Ssm[l], Wl, ed.hptr, ed.hperm, ws.dWedge, ws.dwh, ws.dz)
             else:
                 ops.head_bwd_node(dOn, Pl, ws.Ssm[l], Wl, ws.dP, ws.dz, hseg_ptr=ed.hptr, hperm=ed.hperm,
                                   dWedge=ws.dWedge, dsum=ws.dES if l == 0 else None)
-            Xin = ws.X[l - 1] if l > 0 else P["E"]
-            ws.WaT.copy_(P[f"Wa{l + 1}"].t())
-            ops.gemm_tn_narrow(Xin, ws.dz, G[f"Wa{l + 1}"], G[f"ba{l + 1}"], ws.narrow_slab)
-            # node-level weight gradients of the layer, batched (one launch per L.TN_BATCH): the head-chain
-            # part of dS (added to the edge part, layers 2-3) or dS1, and dK_r = AE_r^T dP_r
-            K, dK = P[f"K{l + 1}"], G[f"K{l + 1}"]
-            sh = self.node_shard
-            tn = [(Xin, dOn, G[f"S{l + 1}"], True) if l > 0 else (P["E"], ws.dES, G["S1"], False)]
-            if sh is None:
-                tn += [(ws.AE[r], ws.dP[r], dK[r], False) for r in range(R)]
-            for i in range(0, len(tn), L.TN_BATCH):
-                ops.gemm_tn_batched(tn[i:i + L.TN_BATCH], ws.tn_slab, **pk)
-            if l > 0:
-                ops.rowgemm(dOn, Sl, dOn_next, b_trans=True, coef=ws.dz, V=ws.WaT, v_rel_stride=D,
-                            v_row_stride=0, act=L.ACT_DSIGMOID, aux=Xin, **pr)
-            else:
-                # dE (head input of layer 1 + x·S1 inputs of both sides)
-                ops.rowgemm(ws.dES, Sl, G["E"], b_trans=True, coef=ws.dz, V=ws.WaT, v_rel_stride=D,
-                            v_row_stride=0, **pr)
-            # relation kernels: dK_r = AE_r^T dP_r (above) ; dAE_r += dP_r K_r^T
-            if sh is None:
-                ops.rowgemm_batched([(ws.dP[r], K[r], ws.dAE[r], dict(b_trans=True, accumulate=(l != 2), **pn))
-                                     for r in range(R)])
-            else:
+            self._wa_transposed(P, ws, l)
+            self._node_bwd(P, G, ws, l, dOn, dOn_next, relations=sh is None)
+            if sh is not None:
                 # relation-sharded: the owners sum the edge partials of dP, then form their rows of dK_r (a
                 # partial over rows, all-reduced with the other small gradients) and of dAE_r
+                K, dK = P[f"K{l + 1}"], G[f"K{l + 1}"]
                 sh.reduce_scatter(ws.dP.view(R * N, D))
                 dK.zero_()
                 for r, n0, n1 in sh.pieces():
-                    ops.gemm_tn(ws.AE[r][n0:n1], ws.dP[r][n0:n1], dK[r], ws.tn_slab, accumulate=True, **pk)
+                    ops.gemm_tn(ws.AE[r][n0:n1], ws.dP[r][n0:n1], dK[r], ws.tn_slab, accumulate=True,
+                                precision=self.gemm)
                 ops.rowgemm_batched([(ws.dP[r][n0:n1], K[r], ws.dAE[r][n0:n1],
-                                      dict(b_trans=True, accumulate=True, **pn)) for r, n0, n1 in sh.pieces()])
+                                      dict(b_trans=True, accumulate=True, precision=self.proj_gemm))
+                                     for r, n0, n1 in sh.pieces()])
             dOn, dOn_next = dOn_next, dOn
-        # DistMult rel grad and the loss: every gradient past E is final now
-        ops.reduce_slabs(ws.drel_slab, ws.nb_dm, G["rel"])
-        ops.reduce_slabs(ws.loss_slab, ws.nb_dm, G.loss)
-        if comm is not None:
-            comm.ready(G.buf[N * D:])
-        # dE += sum_r A_r^T dAE_r  (gradient through all_e -> sparse_dense_matmul); per-row sums, so a
-        # row-chunked launch sequence is bitwise the single launch
-        bptr, bcol, bval = adj.bwd_ptr, adj.bwd_col, adj.bwd_val
-        if self.spmm_shard is not None and self.node_shard is None:
+        self._small_grads_done(G, ws, comm)
+        csr = adj.bwd_ptr, adj.bwd_col, adj.bwd_val
+        if self.spmm_shard is not None and sh is None:
             # the owners of dAE's (relation, row) range get its sums over the ranks; each rank's transposed
             # SpMM runs over the entries in its range only, and dE's all-reduce below adds the ranks' parts
             self.spmm_shard.reduce_scatter(ws.dAE.view(R * N, D))
-            bptr, bcol, bval = adj.bwd_columns(self.spmm_shard.a, self.spmm_shard.b)
-        chunks = comm.row_chunks(N) if comm is not None else [(0, N)]
-        for n0, n1 in chunks:
-            ops.spmm_csr(bptr[n0:n1 + 1], bcol, bval, ws.dAE.view(R * N, D),
-                         G["E"][n0:n1].view(1, n1 - n0, D), 1, n1 - n0, accumulate=True)
+            csr = adj.bwd_columns(self.spmm_shard.a, self.spmm_shard.b)
+        self._de_spmm(G, ws, csr, comm)
+
+    def _tail_head_fused(self, l, rows=None):
+        """Does layer l's tail reduction add the head chain's node terms (Wl[n] dO[n] into dP, dO[n] into dES) before
+        its store, head_dz then finishing the head side?  bf16 edge tables at R = 8, D = 256 (config 5, on MFMAs) and
+        fp32 edge tables at R <= 2, D = 256 (configs 3 / 4; dP and dES bitwise the unfused pair's).  A node-partitioned
+        step takes the bf16 form only, and for layers 2 and 1 only: their head seeds dO[a:b] are final (the node level
+        of the layer above), layer 3's are still on the wire during its tail reduction."""
+        if not (self.fuse_tail_head and self.D == 256):
+            return False
+        if rows is not None:
+            return self.features == "bf16" and self.R == 8 and l < 2
+        return self.node_shard is None and ((self.features == "bf16" and self.R == 8) or
+                                            (self.features == "f32" and self.R <= 2))
+
+    def _tail_bwd(self, P, G, ws, l, tptr, dOn, Wl, Pl, fused, rows=None):
+        """Tail side of layer l's backward: the segment sums dP (tail part), dWedge and, layer 1, the dES tail part over
+        the tail pointers ``tptr`` (of the node rows ``rows``), then the edge GEMMs of layers 2-3.  With ``overlap``
+        (layers 2-3, unpartitioned) the HBM-bound reduction runs on a side stream beside the MFMA-bound dS TN and sigma'
+        GEMM (it reads do, P, Wedge and writes dP, dWedge: nothing those two touch); the side stream first waits for
+        everything queued so far (the previous layer's readers of dP), and the main stream waits for it before
+        returning to the head-side work that reads dP, dWedge."""
+        Sl, pl = P[f"S{l + 1}"], self.use_planes    # x^1, x^2 are planes tables (forward)
+        do = ws.xt[l]                               # do^{l+1}, written over x^{l+1}
+
+        def reduce():
+            Pr, dPr = self._rows(Pl, rows, 1), self._rows(ws.dP, rows, 1)
+            dsum = self._rows(ws.dES, rows) if l == 0 else None
+            if fused:
+                ops.tail_seg_reduce_head(tptr, ws.Wedge[l], do, Pr, dPr, ws.dWedge, self._rows(dOn, rows),
+                                         self._rows(Wl, rows), self._rows(ws.dwh, rows), dsum=dsum)
+            else:
+                ops.tail_seg_reduce(tptr, None, ws.Wedge[l], do, Pr, dPr, ws.dWedge, dsum=dsum)
+
+        side = self._side_stream() if (self.overlap and l > 0 and rows is None) else None
+        if side is not None:
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                reduce()
+        elif rows is None or rows[1] > rows[0]:
+            reduce()
+        if l > 0 and self.sigma_tn_fused:
+            with self._mark("tail_bwd_sigma_tn"):
+                ops.sigma_tn(do, ws.xt[l - 1], Sl, G[f"S{l + 1}"], ws.tn_slab, precision=self.edge_gemm)
+        elif l > 0:
+            # dS^{l+1} (edge part) = x_t^{l}^T do ; do^{l} = (do S^T) * x(1-x), written over x^{l}
+            with self._mark("tail_dS_tn"):
+                ops.gemm_tn(ws.xt[l - 1], do, G[f"S{l + 1}"], ws.tn_slab, a_planes=pl, precision=self.gemm)
+            with self._mark("tail_bwd_gemm"):
+                ops.rowgemm(do, Sl, ws.xt[l - 1], b_trans=True, act=L.ACT_DSIGMOID, aux=ws.xt[l - 1],
+                            planes=L.PLANES_AUX if pl else 0, precision=self.edge_gemm)
+        if side is not None:
+            torch.cuda.current_stream().wait_stream(side)
+
+    def _wa_transposed(self, P, ws, l):
+        ws.WaT.copy_(P[f"Wa{l + 1}"].t())
+
+    def _node_bwd(self, P, G, ws, l, dOn, dOn_next, rows=None, relations=True):
+        """Node-level side of layer l's backward over the node rows, after the head-side kernel has written dz (and
+        _wa_transposed WaT): dWa / dba, the node-level weight gradients batched (one launch per L.TN_BATCH: the
+        head-chain part of dS, added to the edge part, layers 2-3, or dS1; dK_r = AE_r^T dP_r), the head seeds of the
+        layer below (or dE: head input of layer 1 + x·S1 inputs of both sides) and dAE_r += dP_r K_r^T.
+        ``relations`` False leaves dK_r and dAE_r to the caller (relation-sharded tables)."""
+        R, D = self.R, self.D
+        pk, pn, pr = dict(precision=self.gemm), dict(precision=self.proj_gemm), dict(precision=self.row_gemm)
+        Sl, K, dK = P[f"S{l + 1}"], P[f"K{l + 1}"], G[f"K{l + 1}"]
+        Xin, dz = self._rows(ws.X[l - 1] if l > 0 else P["E"], rows), self._rows(ws.dz, rows)
+        seed = self._rows(dOn, rows) if l > 0 else self._rows(ws.dES, rows)
+        ops.gemm_tn_narrow(Xin, dz, G[f"Wa{l + 1}"], G[f"ba{l + 1}"], ws.narrow_slab)
+        tn = [(Xin, seed, G[f"S{l + 1}"], l > 0)]
+        if relations:
+            tn += [(self._rows(ws.AE[r], rows), self._rows(ws.dP[r], rows), dK[r], False) for r in range(R)]
+        for i in range(0, len(tn), L.TN_BATCH):
+            ops.gemm_tn_batched(tn[i:i + L.TN_BATCH], ws.tn_slab, **pk)
+        if l > 0:
+            ops.rowgemm(seed, Sl, self._rows(dOn_next, rows), b_trans=True, coef=dz, V=ws.WaT, v_rel_stride=D,
+                        v_row_stride=0, act=L.ACT_DSIGMOID, aux=Xin, **pr)
+        else:
+            ops.rowgemm(seed, Sl, self._rows(G["E"], rows), b_trans=True, coef=dz, V=ws.WaT, v_rel_stride=D,
+                        v_row_stride=0, **pr)
+        if relations:
+            ops.rowgemm_batched([(self._rows(ws.dP[r], rows), K[r], self._rows(ws.dAE[r], rows),
+                                  dict(b_trans=True, accumulate=(l != 2), **pn)) for r in range(R)])
+
+    def _small_grads_done(self, G, ws, comm):
+        """DistMult's rel gradient and the loss; every gradient past E is final then (``comm`` takes them)."""
+        ops.reduce_slabs(ws.drel_slab, ws.nb_dm, G["rel"])
+        ops.reduce_slabs(ws.loss_slab, ws.nb_dm, G.loss)
+        if comm is not None:
+            comm.ready(G.buf[self.N * self.D:])
+
+    def _de_spmm(self, G, ws, csr, comm=None, rows=None):
+        """dE += sum_r A_r^T dAE_r over the merged transposed CSR ``csr`` (the gradient through all_e ->
+        sparse_dense_matmul), for the rows ``rows`` or in ``comm``'s row chunks, each handed to it as soon as it is
+        written; per-row sums, so a row-chunked launch sequence is bitwise the single launch."""
+        bptr, bcol, bval = csr
+        N, R, D = self.N, self.R, self.D
+        for n0, n1 in [rows] if rows is not None else comm.row_chunks(N) if comm is not None else [(0, N)]:
+            ops.spmm_csr(bptr[n0:n1 + 1], bcol, bval, ws.dAE.view(R * N, D), G["E"][n0:n1].view(1, n1 - n0, D), 1,
+                         n1 - n0, accumulate=True)
             if comm is not None:
                 comm.ready(G["E"][n0:n1].reshape(-1))
 
     # -- node-partitioned step (parallel.NodeShard) -------------------------------
-    def _dm_seed(self, T):
-        if self._pred_seed is None:        # Keras BCE, x 1/num_entities (IDDGCN.py:161-168)
-            return 1.0 / (float(self._t_global or T) * float(self.N)), True
-        return float(self._pred_seed), False
-
     _e_pending = None      # the asynchronous all-gather of E after an owner-row Adam (node-partitioned train_step)
     # node-partitioned train_step with E owned by rows: False (default) completes the all-gather of E before train_step
     # returns, so params are whole for any reader (to_numpy, a checkpoint, predict) or writer (load); True leaves it in
@@ -709,16 +808,15 @@ class Engine:
         rank's scored edges all have their tail there, so the tail chain reads local P / ES1 rows; the edges'
         heads need W^l (all-gathered, N x R) and DistMult X^3 (all-gathered, N x D).  E S^1 and the layer-1 alpha
         read the owned E rows only: they run first, beside a pending all-gather of E (train_step's owner Adam)."""
-        N, R, D, T = self.N, self.R, self.D, ed.T
+        R, D = self.R, self.D
         sh = self.row_shard
-        a, b = sh.a, sh.b
+        a, b = rows = sh.a, sh.b
         E = P["E"]
-        pn = dict(precision=self.proj_gemm)
-        pr = dict(precision=self.row_gemm)
         idx = sh.owned_idx(self.device)
         if b > a:
-            ops.rowgemm(E[a:b], P["S1"], ws.ES1[a:b], **pn)
-            ops.alpha_fwd(E[a:b], P["Wa1"], P["ba1"], ws.Ssm[0][a:b], ws.W[0][a:b])
+            A, S1, C, kw = self._es1(P, ws, rows)
+            ops.rowgemm(A, S1, C, **kw)
+            self._alpha(P, ws, 0, rows)
         parts, self._e_parts = self._e_parts, None
         self.finish_pending()
         if b > a and parts is not None:
@@ -733,55 +831,30 @@ class Engine:
                     kp, kc, kv = ocsr[(r, k)]
                     ops.spmm_csr(kp, kc, kv, E, ws.AE[r][a:b].view(1, b - a, D), 1, b - a, accumulate=i > 0)
         elif b > a:
-            for r in range(R):              # A_r E over the owned rows (IDDGCN.py:69-70)
-                ops.spmm_csr(adj.fwd_ptr[r * (N + 1) + a:r * (N + 1) + b + 1], adj.fwd_col, adj.fwd_val, E,
-                             ws.AE[r][a:b].view(1, b - a, D), 1, b - a)
+            for r in range(R):              # A_r E over the owned rows
+                self._ae(adj, E, ws, r, a, b)
         if parts is not None:
             for h in parts.values():
                 h.wait()
         if b > a:
-            proj = [(ws.AE[r][a:b], P[f"K{l + 1}"][r], ws.P[l, r][a:b], pn) for l in range(NUM_LAYERS)
-                    for r in range(R)]
-            nb = L.ROWGEMM_BATCH
-            for i in range(0, len(proj), nb):
-                ops.rowgemm_batched(proj[i:i + nb])
-        sh.all_gather(ws.W[0])
+            self._rowgemm_batches(self._projections(P, ws, rows))
         # node level first (layers 1-3 over the owned rows, W^l all-gathered as each layer's alpha is known), so
         # that DistMult's head rows X^3 travel while ALL of the tail side runs (the layer-1 combine, the two tail
-        # GEMMs: they read x^l, P^l, ES1 and the gathered W^l, and write x^l, nothing of X^3)
-        if b > a:
-            ops.combine(ws.ES1, ws.W[0][a:b], ws.P[0], ws.X[0][a:b], y_idx=idx, v_idx=idx)
-        for l in (1, 2):
-            if b > a:
-                ops.alpha_fwd(ws.X[l - 1][a:b], P[f"Wa{l + 1}"], P[f"ba{l + 1}"], ws.Ssm[l][a:b], ws.W[l][a:b])
+        # GEMMs: they read x^l, P^l, ES1 and the gathered W^l, and write x^l, nothing of X^3).  ES1 is still needed
+        # by the layer-1 tail combine then: the head chain's scratch table is the head-seed buffer dOn_b, free until
+        # the backward (a training workspace's)
+        for l in range(NUM_LAYERS):
+            if b > a and l > 0:
+                self._alpha(P, ws, l, rows)
             sh.all_gather(ws.W[l])
-            if b > a and R > 2 and D == 256 and ws.train:
-                # as in forward(): the GEMM into a free N x D table (ES1 is still needed by the layer-1 tail combine
-                # below; the head-seed buffer dOn_b is free until the backward), then the row-aligned combine
-                tmp = ws.dOn_b[a:b]
-                ops.rowgemm(ws.X[l - 1][a:b], P[f"S{l + 1}"], tmp, **pr)
-                ops.combine(tmp, ws.W[l][a:b], ws.P[l], ws.X[l][a:b], v_idx=idx)
-            elif b > a:
-                ops.rowgemm(ws.X[l - 1][a:b], P[f"S{l + 1}"], ws.X[l][a:b], coef=ws.W[l][a:b], V=ws.P[l], v_idx=idx,
-                            v_rel_stride=N * D, act=L.ACT_SIGMOID, **pr)
+            if b > a:
+                self._head_layer(P, ws, l, ws.dOn_b if ws.train else None, rows, idx)
         x3 = sh.all_gather(ws.X[2], async_op=True)
-        pl = self.use_planes
-        ops.gather_rows(ws.W[0], ed.h, ws.Wedge[0])
-        ops.combine(ws.ES1, ws.Wedge[0], ws.P[0], ws.xt[0], y_idx=ed.t, v_idx=ed.t, planes_out=pl)
-        for l in (1, 2):
-            ops.gather_rows(ws.W[l], ed.h, ws.Wedge[l])
-            with self._mark("tail_fwd_gemm"):
-                ops.rowgemm(ws.xt[l - 1], P[f"S{l + 1}"], ws.xt[l], coef=ws.Wedge[l], V=ws.P[l], v_idx=ed.t,
-                            v_rel_stride=N * D, act=L.ACT_SIGMOID,
-                            planes=(L.PLANES_A | (L.PLANES_C if l == 1 else 0)) if pl else 0, precision=self.edge_gemm)
+        for l in range(NUM_LAYERS):
+            self._gather_w(ws, l, ed.h, ws.Wedge)
+            self._tail_layer(P, ws, l, ed.t, ws.xt, ws.Wedge)
         x3.wait()
-        if train:
-            scale, bce = self._dm_seed(T)
-            ops.distmult_bce_heads(ed.hptr, ed.hperm, ws.X[2], ws.xt[2], ed.r, P["rel"], ed.y if bce else None,
-                                   ws.xt[2], ws.dOn_a, ws.drel_slab, ws.loss_slab, scale=scale,
-                                   p_out=ws.p if self._want_p else None, s_out=ws.s if self._want_p else None)
-        else:
-            ops.distmult_bce(ws.X[2], ed.h, ws.xt[2], ed.r, P["rel"], p_out=ws.p, s_out=ws.s)
+        self._distmult(P, ed, ws, train)
 
     def _backward_rows(self, P, G, adj, ed, ws, comm, e_owner=False):
         """The backward of a node-partitioned step: the head seeds dO^3 and the dWedge head sums are
@@ -790,49 +863,26 @@ class Engine:
         ``comm`` (the flat gradient buffer's bucketed all-reduce).  ``e_owner``: dE is not all-reduced but
         reduce-scattered to the row owners (asynchronously; the handle is returned, and G["E"][a:b] holds the sums
         once it is waited for), for the owners' Adam (KerasAdam.apply_owned) and an all-gather of E."""
-        N, R, D = self.N, self.R, self.D
+        N, R = self.N, self.R
         sh = self.row_shard
-        a, b = sh.a, sh.b
-        pk, pn, pr = dict(precision=self.gemm), dict(precision=self.proj_gemm), dict(precision=self.row_gemm)
+        a, b = rows = sh.a, sh.b
         if getattr(ws, "ep", None) is None:
             ws.ep = torch.empty(N, R, dtype=torch.float32, device=self.device)
         dOn, dOn_next = ws.dOn_a, ws.dOn_b
         # head seeds dO^3 of the rank's edges -> the heads' owners, travelling while the layer-3 tail side runs (it
         # reads do^3, x^2, P^3, Wedge^3 and writes dP, dWedge, dS^3, do^2: nothing of dO^3)
         seeds = sh.reduce_scatter(dOn, async_op=True)
-        pl = self.use_planes
         # the tail segments of the rank's edges are the owned rows' (edges are taken by tail): the tail reductions
         # run over [a, b) only, their dP / dES rows are the owned ones
         tptr = ed.tptr[a:b + 1]
-        # bf16 edge tables at R = 8, D = 256 (config 5): layers 2 and 1 take the fused tail + head-term reduction (their
-        # head seeds dO[a:b] are final: the node level of the layer above), then head_dz over the owned rows with the
-        # reduce-scattered dWedge head sums; layer 3's head seeds are still on the wire during its tail reduction
-        fuse = self.fuse_tail_head and self.features == "bf16" and R == 8 and D == 256
         for l in (2, 1, 0):
-            Wl, Pl, Sl = ws.W[l], ws.P[l], P[f"S{l + 1}"]
-            do = ws.xt[l]
-            fused = fuse and l < 2
-            if b > a and fused:
-                ops.tail_seg_reduce_head(tptr, ws.Wedge[l], do, Pl[:, a:b], ws.dP[:, a:b], ws.dWedge, dOn[a:b],
-                                         Wl[a:b], ws.dwh[a:b], dsum=ws.dES[a:b] if l == 0 else None)
-            elif b > a:
-                ops.tail_seg_reduce(tptr, None, ws.Wedge[l], do, Pl[:, a:b], ws.dP[:, a:b], ws.dWedge,
-                                    dsum=ws.dES[a:b] if l == 0 else None)
-            if l > 0 and self.sigma_tn_fused:
-                with self._mark("tail_bwd_sigma_tn"):
-                    ops.sigma_tn(do, ws.xt[l - 1], Sl, G[f"S{l + 1}"], ws.tn_slab, precision=self.edge_gemm)
-            elif l > 0:
-                with self._mark("tail_dS_tn"):
-                    ops.gemm_tn(ws.xt[l - 1], do, G[f"S{l + 1}"], ws.tn_slab, a_planes=pl, **pk)
-                with self._mark("tail_bwd_gemm"):
-                    ops.rowgemm(do, Sl, ws.xt[l - 1], b_trans=True, act=L.ACT_DSIGMOID, aux=ws.xt[l - 1],
-                                planes=L.PLANES_AUX if pl else 0, precision=self.edge_gemm)
+            Wl, Pl = ws.W[l], ws.P[l]
+            fused = self._tail_head_fused(l, rows)
+            self._tail_bwd(P, G, ws, l, tptr, dOn, Wl, Pl, fused, rows)
             seeds.wait()
             ops.head_wsum(ed.hptr, ed.hperm, ws.dWedge, ws.ep)
             sh.reduce_scatter(ws.ep)             # dWedge head sums -> the heads' owners
-            K, dK = P[f"K{l + 1}"], G[f"K{l + 1}"]
-            Xin = ws.X[l - 1] if l > 0 else P["E"]
-            ws.WaT.copy_(P[f"Wa{l + 1}"].t())
+            self._wa_transposed(P, ws, l)
             if b > a:
                 if fused:       # dW = dwh + the head sums: head_dz over one-entry "segments" n -> ep[a + n]
                     ops.head_dz(ws.Ssm[l][a:b], Wl[a:b], sh.owned_ptr(self.device), sh.owned_idx(self.device), ws.ep,
@@ -840,52 +890,30 @@ class Engine:
                 else:
                     ops.head_bwd_node(dOn[a:b], Pl[:, a:b], ws.Ssm[l][a:b], Wl[a:b], ws.dP[:, a:b], ws.dz[a:b],
                                       ep=ws.ep[a:b], dsum=ws.dES[a:b] if l == 0 else None)
-                ops.gemm_tn_narrow(Xin[a:b], ws.dz[a:b], G[f"Wa{l + 1}"], G[f"ba{l + 1}"], ws.narrow_slab)
-                tn = [(Xin[a:b], dOn[a:b], G[f"S{l + 1}"], True) if l > 0 else (P["E"][a:b], ws.dES[a:b], G["S1"], False)]
-                tn += [(ws.AE[r][a:b], ws.dP[r][a:b], dK[r], False) for r in range(R)]
-                for i in range(0, len(tn), L.TN_BATCH):
-                    ops.gemm_tn_batched(tn[i:i + L.TN_BATCH], ws.tn_slab, **pk)
-                if l > 0:
-                    ops.rowgemm(dOn[a:b], Sl, dOn_next[a:b], b_trans=True, coef=ws.dz[a:b], V=ws.WaT, v_rel_stride=D,
-                                v_row_stride=0, act=L.ACT_DSIGMOID, aux=Xin[a:b], **pr)
-                else:
-                    ops.rowgemm(ws.dES[a:b], Sl, G["E"][a:b], b_trans=True, coef=ws.dz[a:b], V=ws.WaT,
-                                v_rel_stride=D, v_row_stride=0, **pr)
-                ops.rowgemm_batched([(ws.dP[r][a:b], K[r], ws.dAE[r][a:b],
-                                      dict(b_trans=True, accumulate=(l != 2), **pn)) for r in range(R)])
+                self._node_bwd(P, G, ws, l, dOn, dOn_next, rows)
             else:                                # an empty range: its partials are zero
                 for k in (f"Wa{l + 1}", f"ba{l + 1}", f"K{l + 1}") + (("S1",) if l == 0 else ()):
                     G[k].zero_()
             dOn, dOn_next = dOn_next, dOn
-        ops.reduce_slabs(ws.drel_slab, ws.nb_dm, G["rel"])
-        ops.reduce_slabs(ws.loss_slab, ws.nb_dm, G.loss)
-        if comm is not None:
-            comm.ready(G.buf[N * D:])
+        self._small_grads_done(G, ws, comm)
         # dE: the owned rows' direct terms (above), zero elsewhere, + the transposed SpMM of the owned dAE rows
         G["E"][:a].zero_()
         G["E"][b:].zero_()
-        bptr, bcol, bval = adj.bwd_node_rows(a, b)
+        csr = adj.bwd_node_rows(a, b)
         if e_owner and self.split_e_collectives:
             # split E collectives: the transposed SpMM by destination owner, each owner's dE rows reduced to it as soon
             # as they are written (owner order on every rank)
             hs = []
             for k in range(sh.world):
-                n0, n1 = sh.cuts[k], sh.cuts[k + 1]
-                if n1 > n0:
-                    ops.spmm_csr(bptr[n0:n1 + 1], bcol, bval, ws.dAE.view(R * N, D),
-                                 G["E"][n0:n1].view(1, n1 - n0, D), 1, n1 - n0, accumulate=True)
+                if sh.cuts[k + 1] > sh.cuts[k]:
+                    self._de_spmm(G, ws, csr, rows=(sh.cuts[k], sh.cuts[k + 1]))
                 hs.append(sh.reduce_rows(G["E"], k))
             from .parallel import _All
             return _All(hs)
         if e_owner:
-            ops.spmm_csr(bptr, bcol, bval, ws.dAE.view(R * N, D), G["E"].view(1, N, D), 1, N, accumulate=True)
+            self._de_spmm(G, ws, csr, rows=(0, N))
             return sh.reduce_scatter(G["E"], async_op=True)
-        chunks = comm.row_chunks(N) if comm is not None else [(0, N)]
-        for n0, n1 in chunks:
-            ops.spmm_csr(bptr[n0:n1 + 1], bcol, bval, ws.dAE.view(R * N, D),
-                         G["E"][n0:n1].view(1, n1 - n0, D), 1, n1 - n0, accumulate=True)
-            if comm is not None:
-                comm.ready(G["E"][n0:n1].reshape(-1))
+        self._de_spmm(G, ws, csr, comm)
 
     # -- public steps ---------------------------------------------------------
     def train_step(self, params, grads, opt, adj, ed, t_global=None, comm=None):
@@ -933,43 +961,24 @@ class Engine:
         the head chain X^l, everything a scored edge's tail chain and DistMult read.  ES1 keeps E·S^1 (at R > 2,
         D = 256 forward() reuses it as scratch for X^{l-1}·S^l; here the tail side reads it afterwards, so that
         product goes through a table of its own)."""
-        N, R, D = self.N, self.R, self.D
-        E = P["E"]
-        pn, pr = dict(precision=self.proj_gemm), dict(precision=self.row_gemm)
-        ops.spmm_csr(adj.fwd_ptr, adj.fwd_col, adj.fwd_val, E, ws.AE, R, N)
-        proj = [(ws.AE[r], P[f"K{l + 1}"][r], ws.P[l, r], pn) for l in range(NUM_LAYERS) for r in range(R)]
-        proj.append((E, P["S1"], ws.ES1, pn))
-        for i in range(0, len(proj), L.ROWGEMM_BATCH):
-            ops.rowgemm_batched(proj[i:i + L.ROWGEMM_BATCH])
-        ops.alpha_fwd(E, P["Wa1"], P["ba1"], ws.Ssm[0], ws.W[0])
-        ops.combine(ws.ES1, ws.W[0], ws.P[0], ws.X[0])
-        for l in (1, 2):
-            S = P[f"S{l + 1}"]
-            ops.alpha_fwd(ws.X[l - 1], P[f"Wa{l + 1}"], P[f"ba{l + 1}"], ws.Ssm[l], ws.W[l])
-            if R > 2 and D == 256:
-                if getattr(ws, "xs", None) is None:
-                    ws.xs = torch.empty(N, D, dtype=torch.float32, device=self.device)
-                ops.rowgemm(ws.X[l - 1], S, ws.xs, **pr)
-                ops.combine(ws.xs, ws.W[l], ws.P[l], ws.X[l])
-            else:
-                ops.rowgemm(ws.X[l - 1], S, ws.X[l], coef=ws.W[l], V=ws.P[l], v_rel_stride=N * D,
-                            act=L.ACT_SIGMOID, **pr)
+        self._ae(adj, P["E"], ws)
+        self._rowgemm_batches(self._projections(P, ws) + [self._es1(P, ws)])
+        if self._head_via_scratch and getattr(ws, "xs", None) is None:
+            ws.xs = torch.empty(self.N, self.D, dtype=torch.float32, device=self.device)
+        for l in range(NUM_LAYERS):
+            self._alpha(P, ws, l)
+            self._head_layer(P, ws, l, getattr(ws, "xs", None))
 
     def _screen_layered(self, P, ws, h, r, t, s_out):
         """The tail chain and DistMult of forward() over a dense block of scored edges given by device index arrays
-        (no sort, no segments): the same edge kernels and launch order as forward()'s per-edge part."""
-        N, D, T = self.N, self.D, h.shape[0]
-        pl = self.use_planes
+        (no sort, no segments): the edge stages of forward(), in its order."""
+        T = h.shape[0]
         xt = [ws.xt[l][:T] for l in range(NUM_LAYERS)]
         we = [ws.Wedge[l][:T] for l in range(NUM_LAYERS)]
-        ops.gather_rows(ws.W[0], h, we[0])
-        ops.combine(ws.ES1, we[0], ws.P[0], xt[0], y_idx=t, v_idx=t, planes_out=pl)
-        for l in (1, 2):
-            ops.gather_rows(ws.W[l], h, we[l])
-            ops.rowgemm(xt[l - 1], P[f"S{l + 1}"], xt[l], coef=we[l], V=ws.P[l], v_idx=t, v_rel_stride=N * D,
-                        act=L.ACT_SIGMOID, planes=(L.PLANES_A | (L.PLANES_C if l == 1 else 0)) if pl else 0,
-                        precision=self.edge_gemm)
-        ops.distmult_bce(ws.X[2], h, xt[2], r, P["rel"], p_out=ws.p[:T], s_out=s_out)
+        for l in range(NUM_LAYERS):
+            self._gather_w(ws, l, h, we)
+            self._tail_layer(P, ws, l, t, xt, we)
+        self._distmult_scores(P, ws, h, r, xt[2], ws.p[:T], s_out)
 
     def rank_candidates(self, params, adj, queries, side="tail", k=10, filter_csr=None, return_scores=False,
                         max_edges=1 << 22, fused=None):
@@ -991,24 +1000,16 @@ class Engine:
             raise ValueError(f"side must be 'tail' or 'head', got {side!r}")
         if not 1 <= int(k) <= L.TOPK_MAX:
             raise ValueError(f"k must be in [1, {L.TOPK_MAX}], got {k}")
-        if self.node_shard is not None or self.spmm_shard is not None or self.row_shard is not None:
-            raise L.IddgcnError("rank_candidates: not available on an Engine with node_shard / spmm_shard / row_shard "
-                                "set")
-        N, R, D, dev = self.N, self.R, self.D, self.device
+        self._require_unsharded("rank_candidates")
+        N, D, dev = self.N, self.D, self.device
         k = int(k)
         can_fuse = D <= 64 and self.features == "f32"
         if fused is None:
             fused = can_fuse and self.fused_screen_default
         elif fused and not can_fuse:
             raise L.IddgcnError("rank_candidates: the fused kernel takes D <= 64 with fp32 features")
-        q = np.asarray(queries.cpu() if isinstance(queries, torch.Tensor) else queries).astype(np.int64)
-        if q.ndim != 2 or q.shape[1] != 3:
-            raise L.IddgcnError(f"queries must be (Q, 3), got {q.shape}")
+        q = self._triples(queries, "queries", "query")
         Q = q.shape[0]
-        if Q and (min(q[:, 0].min(), q[:, 2].min()) < 0 or max(q[:, 0].max(), q[:, 2].max()) >= N):
-            raise L.IddgcnError("query entity index out of range [0, num_entities)")
-        if Q and (q[:, 1].min() < 0 or q[:, 1].max() >= R):
-            raise L.IddgcnError("query relation index out of range [0, num_relations)")
         i32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=dev)  # noqa: E731
         node = i32(q[:, 0] if side == "tail" else q[:, 2])
         target = i32(q[:, 2] if side == "tail" else q[:, 0])
@@ -1111,10 +1112,9 @@ class Engine:
             if getattr(self, "_scratch_grads", None) is None:
                 self._scratch_grads = FlatParams(N, R, D, self.device)
             grads = self._scratch_grads
-        if self.node_shard is not None or self.spmm_shard is not None or self.row_shard is not None:
-            # a sharded backward leaves only this rank's rows of dAE (or its reduce-scattered range): the
-            # SDDMM below needs the full per-rank dAE
-            raise L.IddgcnError("value_grads: not available on an Engine with node_shard / spmm_shard / row_shard set")
+        # a sharded backward leaves only this rank's rows of dAE (or its reduce-scattered range): the SDDMM below needs
+        # the full per-rank dAE
+        self._require_unsharded("value_grads")
         self._pred_seed, self._want_p = float(scale), True
         try:
             self.forward(params, adj, ed, ws, True)
@@ -1140,21 +1140,13 @@ class Engine:
         in the caller's entry order, relation after relation, as the concatenation of ``value_grads``' list (rows of
         h relation by relation, then rows of t when t != h) — and ``grad`` (qptr[-1],), the gradient of
         ``scale * p_q`` w.r.t. that entry's value.  Every entry not listed has gradient exactly 0."""
-        if self.node_shard is not None or self.spmm_shard is not None or self.row_shard is not None:
-            raise L.IddgcnError("value_grads_batch: not available on an Engine with node_shard / spmm_shard / "
-                                "row_shard set")
+        self._require_unsharded("value_grads_batch")
         N, R, D, dev = self.N, self.R, self.D, self.device
         if D not in (32, 64) or self.features != "f32":
             raise L.IddgcnError("value_grads_batch takes D in {32, 64} with fp32 features: use value_grads / "
                                 "explain.explaine (the per-triple path) for this engine")
-        q = np.asarray(triples.cpu() if isinstance(triples, torch.Tensor) else triples).astype(np.int64)
-        if q.ndim != 2 or q.shape[1] != 3:
-            raise L.IddgcnError(f"triples must be (Q, 3), got {q.shape}")
+        q = self._triples(triples, "triples", "triple")
         Q = q.shape[0]
-        if Q and (min(q[:, 0].min(), q[:, 2].min()) < 0 or max(q[:, 0].max(), q[:, 2].max()) >= N):
-            raise L.IddgcnError("triple entity index out of range [0, num_entities)")
-        if Q and (q[:, 1].min() < 0 or q[:, 1].max() >= R):
-            raise L.IddgcnError("triple relation index out of range [0, num_relations)")
         if int(max_entries) < 1:
             raise ValueError(f"max_entries must be positive, got {max_entries}")
         i32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=dev)  # noqa: E731

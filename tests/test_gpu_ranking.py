@@ -428,9 +428,10 @@ def test_chunked_calls_are_bitwise(fused, cuda):
 @pytest.mark.parametrize("N,R,D,gemm", [(300, 2, 64, "exact"), (257, 4, 64, "exact"), (150, 2, 256, "bf16x3"),
                                         (100, 3, 256, "exact")])
 def test_node_tables_equal_forwards(N, R, D, gemm, cuda):
-    """Engine._node_tables repeats the node-level launches of Engine.forward: after a predict() and after
-    _node_tables on a fresh workspace, AE, P, W^l, X^l (and ES1, where forward does not reuse it as scratch: R <= 2
-    or D < 256) are bitwise equal.  (100, 3, 256) takes forward's R > 2, D = 256 head-chain form."""
+    """Engine._node_tables runs the node-level stages of Engine.forward (the same stage methods, without the tail side
+    between them), and this pins it: after a predict() and after _node_tables on a fresh workspace, AE, P, W^l, X^l
+    (and ES1, where forward does not reuse it as scratch: R <= 2 or D < 256) are bitwise equal.  (100, 3, 256) takes
+    the R > 2, D = 256 head-chain form, whose scratch table is ES1 in forward and a table of its own here."""
     from iddgcn_amd.engine import Workspace
     pos, _ = synthetic_graph(N, R, 3 * N, seed=3)
     rng = np.random.default_rng(0)
