@@ -378,8 +378,19 @@ class Engine:
     @property
     def edge_gemm(self):
         """Precision of the edge-level row GEMMs (the tail chain's forward and sigma' backward): "bf16" with
-        edge_mfma="bf16" (bf16 edge tables), else ``row_gemm``."""
-        return "bf16" if self.edge_mfma == "bf16" else self.row_gemm
+        edge_mfma="bf16" (bf16 edge tables), else ``row_gemm`` as ``_epilogue_gemm`` reads it.  On bf16 edge tables
+        "exact4" so reads as "exact": both mean the weights as a bf16 hi + lo pair there (include/iddgcn.h
+        IDDGCN_GEMM_BF16), and the fused sigma' + dS pass (iddgcn_sigma_tn_bf16) takes no four-chain precision."""
+        return "bf16" if self.edge_mfma == "bf16" else self._epilogue_gemm
+
+    @property
+    def _epilogue_gemm(self):
+        """``row_gemm`` for a row GEMM with coefficients or a sigma' operand (every edge-level GEMM; the head chain's
+        fused forward and its backward).  At D = 256 the four-chain kernel is the plain form only and
+        iddgcn_rowgemm_f32 refuses "exact4" on any other form (include/iddgcn.h IDDGCN_GEMM_F32_4CHAIN), so there
+        "exact4" reads as "exact": the same f32 MFMA products in one chain."""
+        pr = self.row_gemm
+        return "exact" if (pr == "exact4" and self.D == 256) else pr
 
     @property
     def sigma_tn_fused(self):
@@ -523,7 +534,7 @@ class Engine:
             ops.combine(tmp, W, ws.P[l], Xout, v_idx=idx)
         else:
             ops.rowgemm(Xin, S, Xout, coef=W, V=ws.P[l], v_idx=idx, v_rel_stride=self.N * self.D, act=L.ACT_SIGMOID,
-                        precision=pr)
+                        precision=self._epilogue_gemm)
 
     def _gather_w(self, ws, l, h, we):
         """W^l[h_e]: the per-edge copy of the dynamic weights."""
@@ -710,7 +721,7 @@ class Engine:
         layer below (or dE: head input of layer 1 + x·S1 inputs of both sides) and dAE_r += dP_r K_r^T.
         ``relations`` False leaves dK_r and dAE_r to the caller (relation-sharded tables)."""
         R, D = self.R, self.D
-        pk, pn, pr = dict(precision=self.gemm), dict(precision=self.proj_gemm), dict(precision=self.row_gemm)
+        pk, pn, pr = dict(precision=self.gemm), dict(precision=self.proj_gemm), dict(precision=self._epilogue_gemm)
         Sl, K, dK = P[f"S{l + 1}"], P[f"K{l + 1}"], G[f"K{l + 1}"]
         Xin, dz = self._rows(ws.X[l - 1] if l > 0 else P["E"], rows), self._rows(ws.dz, rows)
         seed = self._rows(dOn, rows) if l > 0 else self._rows(ws.dES, rows)
