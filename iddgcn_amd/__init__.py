@@ -12,7 +12,7 @@ from .graph import get_adj_mats  # noqa: F401
 from .model import (Adam, BinaryCrossentropy, DistMult, IDDGCN_Layer, IDDGCN_Model,  # noqa: F401
                     SaveWeightsCallback, get_IDDGCN_Model)
 from .utils import generate_reverse_triplets, get_y_true  # noqa: F401
-from .metrics import classification_metrics, ranking_metrics  # noqa: F401
+from .metrics import classification_metrics, classification_metrics_device, ranking_metrics  # noqa: F401
 from . import explain  # noqa: F401,E402  (explaiNE / GNNExplainer / IDDGCN explainer on the HIP path)
 from . import similarity  # noqa: F401,E402  (feat_similarity.py similarity graph on MFMA)
 from . import ground_truth  # noqa: F401,E402  (explanation ground truth on the GPU, P/R/F1@k of the explainers)

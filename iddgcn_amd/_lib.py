@@ -1,5 +1,6 @@
 """ctypes binding of libiddgcn_hip.so (C-ABI declared in include/iddgcn.h, iddgcn_graph.h,
-iddgcn_similarity.h, iddgcn_sampling.h, iddgcn_screen.h, iddgcn_explain.h and iddgcn_ground_truth.h).
+iddgcn_similarity.h, iddgcn_sampling.h, iddgcn_screen.h, iddgcn_explain.h, iddgcn_ground_truth.h and
+iddgcn_metrics.h).
 
 The product path has no CPU fallback: if the shared library is missing, was
 built for another ABI version or from other sources than the tree beside it
@@ -151,7 +152,17 @@ SIGNATURES = {
     "iddgcn_ground_truth_count": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "iddgcn_gt_exclusive_scan": (ci, [vp, ci, vp, vp]),
     "iddgcn_ground_truth_fill": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp]),
+    # include/iddgcn_metrics.h (classification metrics on the device; added symbols only)
+    "iddgcn_clf_metrics_workspace": (cll, [cll, ci]),
+    "iddgcn_clf_metrics": (ci, [vp, cll, ci, vp, vp, vp, ctypes.c_double, vp, vp, vp, cll]),
+    "iddgcn_keep_best_f32": (ci, [vp, cll, vp, vp, vp, ci, vp, vp, vp, vp]),
+    "iddgcn_clf_history_append": (ci, [vp, ci, ci, vp, vp, vp, vp, ci, vp]),
 }
+# include/iddgcn_metrics.h: IDDGCN_CLF_*
+CLF_SMALL_MAX, CLF_MAX_GROUPS = 4096, 64
+CLF_COUNTS = ("tp", "tn", "fp", "fn", "n_pos", "n_neg", "auc_num2", "n_thresholds", "status")
+CLF_VALUES = ("accuracy", "recall", "precision", "specificity", "f1", "roc_auc", "aupr", "bce")
+CLF_ST_NO_POS, CLF_ST_NO_NEG, CLF_ST_BAD_INPUT = 1, 2, 4
 GT_LIST_CAPACITY = 8192      # IDDGCN_GT_LIST_CAPACITY
 
 _lib = None

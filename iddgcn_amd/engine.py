@@ -218,6 +218,88 @@ class GraphedTrainStep:
         return self.losses[self.done - 1]
 
 
+class DeviceValidation:
+    """Held-out metrics without a host read: the train=False forward on the validation edges, iddgcn_clf_metrics on
+    the probabilities where the forward leaves them (ws.p with ed.y / ed.r, the tail-sorted order: the metrics do
+    not depend on the order, so nothing is unsorted), the result appended to device histories indexed by a device
+    counter and, with ``keep`` = (index into the flat values, mode), iddgcn_keep_best_f32 on params.flat.
+
+    ``run()`` issues the launches on the current stream; ``replay()`` replays them from a HIP graph captured on
+    its first call (after GraphedTrainStep.replay() on a validating epoch) with the same pointers, so either way
+    gives bitwise the same numbers.  The object owns its Workspace, as GraphedTrainStep does."""
+
+    def __init__(self, eng, params, adj, ed, capacity, threshold=0.5, groups=0, keep=None):
+        dev = eng.device
+        self.eng, self.params, self.adj, self.ed = eng, params, adj, ed
+        self.G, self.threshold, self.keep = int(groups), float(threshold), keep
+        self.ws = Workspace(eng.N, eng.R, eng.D, ed.T, dev, False, eng.edge_dtype)
+        self.counts = torch.zeros((1 + self.G, len(L.CLF_COUNTS)), dtype=torch.int64, device=dev)
+        self.values = torch.zeros((1 + self.G, len(L.CLF_VALUES)), dtype=torch.float64, device=dev)
+        self.mws = ops.clf_metrics_workspace(ed.T, self.G, dev)
+        cap = max(int(capacity), 1)
+        self.hist_counts = torch.zeros((cap, self.counts.numel()), dtype=torch.int64, device=dev)
+        self.hist_values = torch.zeros((cap, self.values.numel()), dtype=torch.float64, device=dev)
+        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.capacity, self.done = cap, 0
+        if keep is not None:
+            self.best = torch.empty_like(params.flat)
+            self.best_value = torch.full((1,), float("nan"), dtype=torch.float64, device=dev)
+            self.best_index = torch.full((1,), -1, dtype=torch.int32, device=dev)
+            self.improved = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.graph = None
+
+    def _metrics(self):
+        self.eng.forward(self.params, self.adj, self.ed, self.ws, False)
+        ops.clf_metrics(self.ws.p, self.ed.y, self.ed.r if self.G else None, self.G, self.threshold, self.counts,
+                        self.values, self.mws)
+
+    def _body(self):
+        self._metrics()
+        if self.keep is not None:
+            i, mode = self.keep
+            ops.keep_best(self.params.flat, self.best, self.values.view(-1)[i:i + 1], mode, self.best_value,
+                          self.best_index, self.counter, self.improved)
+        ops.clf_history_append(self.counts.view(-1), self.values.view(-1), self.hist_counts, self.hist_values,
+                               self.counter)
+
+    def _advance(self):
+        if self.done >= self.capacity:
+            raise L.IddgcnError("DeviceValidation: history full")
+        self.done += 1
+
+    def run(self):
+        self._advance()
+        self.eng.finish_pending()
+        self._body()
+
+    def replay(self):
+        self._advance()
+        if self.graph is None:
+            # every kernel of the body has run once before the capture: the forward and the metrics, which only write
+            # this object's workspace and outputs again (the two small kernels share the metrics' code object)
+            self._metrics()
+            torch.cuda.synchronize(self.eng.device)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self._body()
+        self.graph.replay()
+
+    def last(self):
+        """(counts, values) of the latest validation as host lists: one synchronising read."""
+        return self.counts.cpu().tolist(), self.values.cpu().tolist()
+
+    def histories(self):
+        """(counts, values) of every validation so far, (done, slots, 9) and (done, slots, 8) host lists."""
+        k = self.done
+        return (self.hist_counts[:k].view(k, 1 + self.G, -1).cpu().tolist(),
+                self.hist_values[:k].view(k, 1 + self.G, -1).cpu().tolist())
+
+    def best_state(self):
+        """(validation index, value) of the kept parameters, or (None, None) if no validation improved."""
+        i = int(self.best_index.item())
+        return (i, float(self.best_value.item())) if i >= 0 else (None, None)
+
+
 class Workspace:
     """Every device buffer one step needs, sized for (N, R, D, T).
 

@@ -1,5 +1,7 @@
-"""Evaluation metrics on the host (numpy only).
+"""Evaluation metrics: on the host (numpy only), and the classification block on the GPU.
 
+``classification_metrics_device`` is ``classification_metrics`` computed by iddgcn_clf_metrics on tensors that stay
+on the device (what IDDGCN_Model.evaluate and fit's validation run); torch is imported only there.
 ``ranking_metrics`` summarises the ranks Engine.rank_candidates / IDDGCN_Model.rank_candidates return (MRR, mean
 rank, Hits@k); ``classification_metrics`` is the reference's evaluation block (IDDGCN_eval.py:71-84: confusion
 counts at a threshold, accuracy, recall, precision, specificity, F1, ROC-AUC, and AUPR as the trapezoid over the
@@ -63,3 +65,51 @@ def classification_metrics(y_true, y_prob, threshold=0.5):
             "recall": float(recall), "precision": float(precision),
             "specificity": tn / (tn + fp), "f1": float(f1),
             "roc_auc": roc_auc, "aupr": -_trapezoid(reca, prec)}
+
+
+def slot_dicts(counts, values):
+    """The (slots, 9) integer and (slots, 8) double outputs of iddgcn_clf_metrics (host arrays or lists) as one dict
+    per slot: classification_metrics' keys plus bce, auc_num2, n_thresholds, n_pos, n_neg and status."""
+    from ._lib import CLF_COUNTS, CLF_VALUES
+    out = []
+    for c, v in zip(counts, values):
+        d = {k: int(x) for k, x in zip(CLF_COUNTS, c)}
+        d.update({k: float(x) for k, x in zip(CLF_VALUES, v)})
+        out.append(d)
+    return out
+
+
+def classification_metrics_device(y_true, y_prob, threshold=0.5, groups=None, num_groups=0):
+    """classification_metrics on the GPU (iddgcn_clf_metrics): ``y_prob`` a float32 CUDA tensor, ``y_true`` a CUDA
+    tensor of 0 / 1 labels, both left on the device; the one host read is the result.  Returns the dict of every
+    element: classification_metrics' keys, plus ``bce`` (the mean Keras binary cross-entropy), ``auc_num2`` (the
+    exact integer with roc_auc = auc_num2 / (2 n_pos n_neg)), ``n_thresholds`` (distinct scores), ``n_pos``,
+    ``n_neg`` and ``status``.  With ``groups`` (int CUDA tensor) and ``num_groups`` = G it returns a list of 1 + G such
+    dicts: every element, then the elements of group 0 .. G - 1 (an id outside [0, G) counts in the first only).
+
+    Scores are ranked by their float32 bits, as the reference ranks model.predict's output.  Unlike the host
+    function this does not raise on a set with one class only: the ratios without a denominator are NaN and
+    ``status`` says why (1: no positives, 2: no negatives, 4: a NaN / out-of-range probability or a label outside
+    {0, 1} was seen)."""
+    import torch
+
+    from . import ops
+    if not (isinstance(y_prob, torch.Tensor) and y_prob.is_cuda and y_prob.dtype == torch.float32):
+        raise ValueError("classification_metrics_device: y_prob must be a float32 CUDA tensor")
+    if not (isinstance(y_true, torch.Tensor) and y_true.is_cuda):
+        raise ValueError("classification_metrics_device: y_true must be a CUDA tensor")
+    p = y_prob.reshape(-1).contiguous()
+    y = y_true.reshape(-1).to(torch.float32).contiguous()
+    if p.numel() == 0 or p.numel() != y.numel():
+        raise ValueError("classification_metrics_device: y_true and y_prob must be non-empty and of one length")
+    G = int(num_groups) if groups is not None else 0
+    g = None
+    if groups is not None:
+        if G < 1:
+            raise ValueError("classification_metrics_device: groups needs num_groups >= 1")
+        g = groups.reshape(-1).to(torch.int32).contiguous()
+        if g.numel() != p.numel():
+            raise ValueError("classification_metrics_device: groups must be as long as y_prob")
+    counts, values = ops.clf_metrics(p, y, g, G, threshold)
+    d = slot_dicts(counts.cpu().tolist(), values.cpu().tolist())
+    return d if groups is not None else d[0]

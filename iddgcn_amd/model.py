@@ -22,7 +22,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .engine import NUM_LAYERS, Engine, FlatParams, GraphedTrainStep, KerasAdam
+from .engine import NUM_LAYERS, DeviceValidation, Engine, FlatParams, GraphedTrainStep, KerasAdam
 from .graph import DeviceAdjacency, SparseAdj, get_adj_mats  # noqa: F401  (re-export)
 from .parallel import BucketedAllReduce, shard_triples, world
 
@@ -288,6 +288,7 @@ class IDDGCN_Model:
         self.neg_path_template = "../datasets/prediction_datasets/mode{mode}_fold{fold}_X_train_neg.npy"
         self.optimizer = None
         self.stop_training = False
+        self.best_epoch = self.best_value = None    # fit(keep_best=...): the kept epoch (1-based) and its value
         self._engine = None
         self._dev = None
         self._opt_state = None
@@ -420,6 +421,44 @@ class IDDGCN_Model:
         _, s = eng.predict(self._params, dadj, ed, logits=True)
         return s.detach().cpu().numpy().reshape(1, -1)
 
+    def _labelled(self, x, y, what):
+        """(h, r, t, adj, labels) of ``x`` (the list predict takes) and ``y`` ((1, B) or (B,) labels); host checks
+        only, so a bad call is refused before anything touches the GPU."""
+        h, r, t, adj = self._unpack(x)
+        lab = np.asarray(y.cpu() if isinstance(y, torch.Tensor) else y, dtype=np.float32)
+        if lab.ndim == 2 and lab.shape[0] == 1:
+            lab = lab[0]
+        if lab.ndim != 1 or not (len(lab) == len(h) == len(r) == len(t)):
+            raise ValueError(f"{what}: y must hold one label per scored triple ({len(h)}), got shape "
+                             f"{np.asarray(y).shape}")
+        if len(lab) == 0:
+            raise ValueError(f"{what}: no triples")
+        return h, r, t, adj, lab
+
+    def evaluate(self, x, y, threshold=0.5, per_relation=False):
+        """The evaluation block of IDDGCN_eval.py:58-122 (``evaluate_model``) on the GPU: the forward of predict,
+        then iddgcn_clf_metrics on the probabilities where the forward leaves them; the one host read is the
+        result.  ``x`` is the list predict takes, ``y`` the (1, B) or (B,) labels.  Returns
+        classification_metrics_device's dict of all triples (tp, tn, fp, fn at ``prob > threshold``, accuracy,
+        recall, precision, specificity, f1, roc_auc, aupr, bce, auc_num2, n_thresholds, n_pos, n_neg, status); with
+        ``per_relation`` it also holds "relation_0" .. "relation_{R-1}", the same dict over each relation's triples
+        (NaN ratios and a status bit where a relation has one class only, no exception)."""
+        h, r, t, adj, lab = self._labelled(x, y, "evaluate")
+        from .metrics import slot_dicts
+        eng = self._device_state()
+        dadj = self._adjacency(adj)
+        ed = eng.edges(np.stack([h, r, t], 1), lab)
+        eng.finish_pending()
+        ws = eng.workspace(ed.T, False)
+        eng.forward(self._params, dadj, ed, ws, False)
+        G = self.num_relations if per_relation else 0
+        counts, values = ops.clf_metrics(ws.p, ed.y, ed.r if G else None, G, threshold)
+        slots = slot_dicts(counts.cpu().tolist(), values.cpu().tolist())
+        out = slots[0]
+        for g, d in enumerate(slots[1:]):
+            out[f"relation_{g}"] = d
+        return out
+
     def rank_candidates(self, x, side="tail", k=10, filter_triples=None, return_scores=False, **kw):
         """Rank every entity as the partner of each triple of ``x`` (the list predict takes): side "tail" scores
         (h, r, c) for all c with target t, "head" scores (c, r, t) with target h, by the logit predict_logits
@@ -461,11 +500,54 @@ class IDDGCN_Model:
         neg = neg[0] if neg.ndim == 3 else neg
         return neg.astype(np.int64)
 
-    def fit(self, x=None, y=None, epochs=1, batch_size=None, verbose=1, callbacks=None, **kwargs):
+    @staticmethod
+    def _val_logs(slot):
+        """One validation's dict as Keras-style logs: val_<key> for every key, and val_loss = the mean BCE."""
+        logs = {f"val_{k}": v for k, v in slot.items()}
+        logs["val_loss"] = slot["bce"]
+        return logs
+
+    @staticmethod
+    def _keep_best_key(keep_best):
+        """(index into iddgcn_clf_metrics' values, mode) of a ``keep_best`` key: val_loss / val_bce take the minimum,
+        every other val_<ratio> the maximum."""
+        names = {f"val_{k}": i for i, k in enumerate(L.CLF_VALUES)}
+        names["val_loss"] = names["val_bce"]
+        if keep_best not in names:
+            raise ValueError(f"keep_best must be one of {sorted(names)}, got {keep_best!r}")
+        return names[keep_best], int(keep_best in ("val_loss", "val_bce"))
+
+    def fit(self, x=None, y=None, epochs=1, batch_size=None, verbose=1, callbacks=None, validation_data=None,
+            validation_freq=1, keep_best=None, **kwargs):
         """Full-batch training (IDDGCN.py:399-412): each epoch is ONE train_step
         over all positives (x) and the negatives of the .npy file (IDDGCN.py:128-160).
         ``batch_size`` has no effect, exactly as in the reference (leading dim 1).
-        Under torch.distributed the scored edges are sharded over ranks."""
+        Under torch.distributed the scored edges are sharded over ranks.
+
+        ``validation_data`` = (x_val, y_val): x_val the list predict takes, with its own adjacency (the reference
+        evaluates on train + test positives, IDDGCN_eval.py:49-50), y_val its labels.  After the step of every
+        ``validation_freq``-th epoch the train=False forward and the metrics kernel run on it (``evaluate``'s
+        numbers at threshold 0.5, bitwise) into device histories: nothing is read on the host, and on the graph
+        path it is a second captured graph replayed after the step's.  The history gets val_loss (the mean BCE),
+        val_roc_auc, val_aupr, val_accuracy, val_f1, ... on those epochs; with ``verbose`` or a callback other than
+        History the same keys are in each such epoch's ``logs`` as floats (a callback may set
+        ``model.stop_training``).  ``keep_best`` = one of those val_* ratios (val_loss: smallest, the others:
+        largest) keeps the parameters of the first epoch with the best value on the device and makes them the
+        model's after the loop, with ``model.best_epoch`` (1-based) and ``model.best_value``; Adam's moments are
+        not kept, so a later fit continues with the moments of the last epoch.  Every rank of a distributed run
+        validates on the whole validation set.  Without validation_data nothing here runs."""
+        val = None
+        if keep_best is not None:
+            keep = self._keep_best_key(keep_best)
+            if validation_data is None:
+                raise ValueError("keep_best needs validation_data")
+        if validation_data is not None:
+            if len(validation_data) != 2:
+                raise ValueError("validation_data must be (x_val, y_val)")
+            if int(validation_freq) < 1:
+                raise ValueError("validation_freq must be >= 1")
+            validation_freq = int(validation_freq)
+            val = self._labelled(validation_data[0], validation_data[1], "fit(validation_data)")
         eng = self._device_state()
         if self.optimizer is None:
             self.compile()
@@ -488,8 +570,17 @@ class IDDGCN_Model:
             cb.set_model(self)
         T = len(triples)
         graphed = None
+        validator, val_epochs = None, []
+        if val is not None and epochs // validation_freq > 0:
+            from .metrics import slot_dicts
+            vh, vr, vt, vadj, vlab = val
+            # the validation graph beside the training one (not through the one-entry cache of _adjacency)
+            vdadj = vadj if isinstance(vadj, DeviceAdjacency) else DeviceAdjacency(list(vadj), self.num_entities,
+                                                                                  self._dev)
+            validator = DeviceValidation(eng, self._params, vdadj, eng.edges(np.stack([vh, vr, vt], 1), vlab),
+                                         epochs // validation_freq, keep=keep if keep_best is not None else None)
         # per-epoch host work only when someone looks at it: else the replays run back to back and
-        # the losses are read once at the end
+        # the losses (and the validation histories) are read once at the end
         lazy = not verbose and all(isinstance(cb, History) for cb in cbs)
         pending = []
         for epoch in range(epochs):
@@ -501,13 +592,23 @@ class IDDGCN_Model:
             else:
                 loss_sum = eng.train_step(self._params, self._grads, self._opt_state, dadj, ed, t_global=T,
                                           comm=comm)
+            validating = validator is not None and (epoch + 1) % validation_freq == 0
+            if validating:
+                val_epochs.append(epoch)
+                if graphed is not None:
+                    validator.replay()
+                else:
+                    validator.run()
             if lazy:
                 pending.append(loss_sum if graphed is not None else loss_sum.clone())
                 continue
             loss = float(loss_sum.item()) / T
-            if verbose and rank == 0:
-                print(f"Epoch {epoch + 1}/{epochs} - loss: {loss:.6f}")
             logs = {"loss": loss}
+            if validating:
+                logs.update(self._val_logs(slot_dicts(*validator.last())[0]))
+            if verbose and rank == 0:
+                print(f"Epoch {epoch + 1}/{epochs} - " + " - ".join(
+                    f"{k}: {logs[k]:.6f}" for k in ("loss", "val_loss", "val_roc_auc", "val_aupr") if k in logs))
             if any(isinstance(cb, SaveWeightsCallback) and epoch + 1 in cb.save_epochs for cb in cbs):
                 self._sync_to_host()
             for cb in cbs:
@@ -515,8 +616,19 @@ class IDDGCN_Model:
             if self.stop_training:
                 break
         if pending:
+            val_logs = {}
+            if val_epochs:
+                val_logs = {e: self._val_logs(slot_dicts(c, v)[0])
+                            for e, c, v in zip(val_epochs, *validator.histories())}
             for epoch, l in enumerate(torch.cat([x.reshape(1) for x in pending]).cpu().tolist()):
-                history.on_epoch_end(epoch, {"loss": l / T})
+                history.on_epoch_end(epoch, {"loss": l / T, **val_logs.get(epoch, {})})
+        if keep_best is not None:
+            # the parameters of the best validating epoch become the model's (the Adam moments stay the last epoch's)
+            i, v = validator.best_state() if validator is not None else (None, None)
+            self.best_epoch = None if i is None else val_epochs[i] + 1
+            self.best_value = v
+            if i is not None:
+                self._params.flat.copy_(validator.best)
         self._sync_to_host()
         return history
 

@@ -1092,3 +1092,75 @@ def ground_truth_fill(queries, mu, drug, dc, N, R, ptr, total, drug_rel, mu_rel)
     L.check(L.lib().iddgcn_ground_truth_fill(_stream(), Q, N, R, _ptr(queries), *_gt_tables(mu, drug, dc, N, R),
                                              _ptr(ptr), int(drug_rel), int(mu_rel), _ptr(out)), "ground_truth_fill")
     return out[:int(total)]
+
+
+# -- classification metrics on the device (include/iddgcn_metrics.h) -----------------------------
+_F64 = torch.float64
+
+
+def clf_metrics_workspace(n, G, device):
+    """The workspace tensor iddgcn_clf_metrics needs for n elements and G groups (one byte at the least)."""
+    nbytes = L.lib().iddgcn_clf_metrics_workspace(int(n), int(G))
+    if nbytes < 0:
+        raise L.IddgcnError(f"clf_metrics: n must be in [0, 2^31) and G in [0, {L.CLF_MAX_GROUPS}], got n={n}, G={G}")
+    return torch.empty(max(int(nbytes), 1), dtype=_U8, device=device)
+
+
+def clf_metrics(prob, label, group=None, G=0, threshold=0.5, counts=None, values=None, workspace=None):
+    """iddgcn_clf_metrics: ``counts`` (1 + G, 9) int64 in the order of L.CLF_COUNTS and ``values`` (1 + G, 8) float64
+    in the order of L.CLF_VALUES, of float32 probabilities / labels and int32 group ids (slot 0: every element,
+    slot g + 1: group g).  Outputs and workspace are allocated unless given (a captured graph passes its own)."""
+    _req(prob, _F32, None, "prob")
+    n = prob.numel()
+    if n < 1:
+        raise L.IddgcnError("clf_metrics: no elements")
+    _req(label, _F32, None, "label")
+    if label.numel() != n:
+        raise L.IddgcnError("clf_metrics: prob and label must be of one length")
+    G = int(G)
+    if G > 0:
+        if group is None:
+            raise L.IddgcnError("clf_metrics: G > 0 needs group ids")
+        _req(group, _I32, None, "group")
+        if group.numel() != n:
+            raise L.IddgcnError("clf_metrics: prob and group must be of one length")
+    if counts is None:
+        counts = torch.empty((1 + G, len(L.CLF_COUNTS)), dtype=_I64, device=prob.device)
+    if values is None:
+        values = torch.empty((1 + G, len(L.CLF_VALUES)), dtype=_F64, device=prob.device)
+    _req(counts, _I64, (1 + G, len(L.CLF_COUNTS)), "counts")
+    _req(values, _F64, (1 + G, len(L.CLF_VALUES)), "values")
+    if workspace is None:
+        workspace = clf_metrics_workspace(n, G, prob.device)
+    _req(workspace, _U8, None, "workspace")
+    L.check(L.lib().iddgcn_clf_metrics(_stream(), n, G, _ptr(prob), _ptr(label), _ptr(group) if G > 0 else None,
+                                       float(threshold), _ptr(counts), _ptr(values), _ptr(workspace),
+                                       workspace.numel()), "clf_metrics")
+    return counts, values
+
+
+def keep_best(params, best, value, mode, best_value, best_epoch, epoch, improved):
+    """iddgcn_keep_best_f32: best <- params if the device double ``value`` strictly improves on ``best_value``
+    (mode 0: larger, 1: smaller; anything but a NaN improves while best_epoch < 0)."""
+    _req(params, _F32, None, "params")
+    _req(best, _F32, tuple(params.shape), "best")
+    for t, nm in ((value, "value"), (best_value, "best_value")):
+        _req(t, _F64, (1,), nm)
+    for t, nm in ((best_epoch, "best_epoch"), (epoch, "epoch"), (improved, "improved")):
+        _req(t, _I32, (1,), nm)
+    L.check(L.lib().iddgcn_keep_best_f32(_stream(), params.numel(), _ptr(params), _ptr(best), _ptr(value), int(mode),
+                                         _ptr(best_value), _ptr(best_epoch), _ptr(epoch), _ptr(improved)),
+            "keep_best")
+
+
+def clf_history_append(counts, values, hist_counts, hist_values, counter):
+    """hist_*[counter] = counts / values; counter += 1 (nothing once the history is full)."""
+    _req(counts, _I64, None, "counts")
+    _req(values, _F64, None, "values")
+    cap = hist_counts.shape[0]
+    _req(hist_counts, _I64, (cap, counts.numel()), "hist_counts")
+    _req(hist_values, _F64, (cap, values.numel()), "hist_values")
+    _req(counter, _I32, (1,), "counter")
+    L.check(L.lib().iddgcn_clf_history_append(_stream(), counts.numel(), values.numel(), _ptr(counts), _ptr(values),
+                                              _ptr(hist_counts), _ptr(hist_values), cap, _ptr(counter)),
+            "clf_history_append")

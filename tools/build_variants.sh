@@ -13,7 +13,7 @@ while [ $# -ge 2 ]; do
       iddgcn_amd/csrc/iddgcn_hip.hip -o $VD/$name.o && \
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $VD/$name.o build/graph_build.hip.o \
       build/similarity.hip.o build/sampling.hip.o build/screen.hip.o build/explain.hip.o \
-      build/ground_truth.hip.o -o $VD/$name.so && rm $VD/$name.o && echo "built $name" ) &
+      build/ground_truth.hip.o build/metrics.hip.o -o $VD/$name.so && rm $VD/$name.o && echo "built $name" ) &
   pids+=($!)
 done
 for p in "${pids[@]}"; do wait $p; done
