@@ -4588,6 +4588,88 @@ __global__ void step_advance_kernel(int* __restrict__ step, float* __restrict__ 
     *step = s + 1;
 }
 
+// ===========================================================================
+// Host side: dispatch on the kernels' template arguments, launch geometry, the row-GEMM plan
+// ===========================================================================
+template <int N>
+using Int = std::integral_constant<int, N>;
+
+// f(Int<D>{}) for the feature width d.  The entries check dim_ok(d) first (anything else would run as 256).
+template <class F>
+void for_width(int d, F&& f) {
+    switch (d) {
+        case 32: f(Int<32>{}); break;
+        case 64: f(Int<64>{}); break;
+        case 128: f(Int<128>{}); break;
+        default: f(Int<256>{}); break;
+    }
+}
+// f(Int<R>{}) for the relation count R = LO..8, LO = 0 or 1.  The entries check the range first (anything else
+// would run as 8).
+template <int LO, class F>
+void for_rel(int R, F&& f) {
+    static_assert(LO == 0 || LO == 1, "relation counts start at 0 or 1");
+    if constexpr (LO == 0) {
+        if (R == 0) {
+            f(Int<0>{});
+            return;
+        }
+    }
+    switch (R) {
+        case 1: f(Int<1>{}); break;
+        case 2: f(Int<2>{}); break;
+        case 3: f(Int<3>{}); break;
+        case 4: f(Int<4>{}); break;
+        case 5: f(Int<5>{}); break;
+        case 6: f(Int<6>{}); break;
+        case 7: f(Int<7>{}); break;
+        default: f(Int<8>{}); break;
+    }
+}
+// f(Int<RT>{}) for the smallest of 1 / 2 / 4 / 8 relation slots that holds R
+template <class F>
+void for_rel_bucket(int R, F&& f) {
+    if (R <= 1) f(Int<1>{});
+    else if (R <= 2) f(Int<2>{});
+    else if (R <= 4) f(Int<4>{});
+    else f(Int<8>{});
+}
+
+inline unsigned grid_for(long long rows, int lpr) {
+    const long long threads = rows * lpr;
+    return (unsigned)((threads + 255) / 256);
+}
+
+// M rows in tiles of tile_rows, shared out over at most max_blocks persistent workgroups that take the same number
+// of tiles each (the last one what is left).  No tiles: {0, 1}.
+struct TileSplit {
+    long long blocks;
+    int tiles_per_block;
+};
+TileSplit split_tiles(long long M, int tile_rows, long long max_blocks) {
+    const long long nt = (M + tile_rows - 1) / tile_rows;
+    const long long nb = nt < max_blocks ? nt : max_blocks;
+    if (nb < 1) return {0, 1};
+    const int tpb = (int)((nt + nb - 1) / nb);
+    return {(nt + tpb - 1) / tpb, tpb};
+}
+
+// rows of a TN GEMM's M per partial-product workgroup: a multiple of the 32-row tile, at least one tile
+long long tn_rows_per_block(long long M, long long n_blocks) {
+    const long long rpb = ((M + n_blocks - 1) / n_blocks + 31) / 32 * 32;
+    return rpb < 32 ? 32 : rpb;
+}
+// the operand precisions of the fp32-table TN entries
+bool tn_precision_ok(int precision) {
+    return precision == IDDGCN_GEMM_EXACT_F32 || precision == IDDGCN_GEMM_SPLIT_F16 || precision == IDDGCN_GEMM_BF16X3;
+}
+// after a TN kernel wrote n_slabs partial d x d products: their sum in slab order into C
+int reduce_tn_slabs(hipStream_t st, int n_slabs, int d, const float* slab, float* C, int accumulate) {
+    if (const int rc = launch_status()) return rc;
+    launch_reduce_slabs(st, n_slabs, (long long)d * d, slab, C, accumulate, 1.0f);
+    return launch_status();
+}
+
 // ---- D = 256 row-GEMM variant selection (rowgemm256_v3_kernel) ----
 struct V3Sel {
     int nv;                 // gathered V tables (template NV)
@@ -4601,6 +4683,9 @@ struct V3Sel {
                c4 == o.c4;
     }
 };
+// V slabs of a gathered combine.  R <= 2: exactly R slabs; more relations: capped slabs (rows past the cap of a
+// tile come from L2)
+int v3_slabs(int R) { return R <= 2 ? R : (R <= 4 ? 4 : 8); }
 // Which v3 instantiation computes this call, or false (the register-staged rowgemm_kernel<256> then runs:
 // a gathered V with the sigma' epilogue, or V rows that are not dense D-float rows).
 bool v3_select(const RowGemmP& p, V3Sel& sel) {
@@ -4608,8 +4693,7 @@ bool v3_select(const RowGemmP& p, V3Sel& sel) {
     const bool dsig = p.act == IDDGCN_ACT_DSIGMOID;
     if (gatherV) {
         if (dsig || p.v_row_stride != 256) return false;
-        // R <= 2: exactly R slabs; more relations: capped slabs (rows past the cap of a tile come from L2)
-        sel = {p.R <= 2 ? p.R : (p.R <= 4 ? 4 : 8), false, true};
+        sel = {v3_slabs(p.R), false, true};
     } else {
         sel = {0, dsig, p.R > 0, p.R > 2};
     }
@@ -4664,72 +4748,122 @@ int check_rowgemm(const iddgcn_rowgemm_t& a) {
 // The bf16x3 row GEMM's forms (rowgemm256_b3_kernel<NV, AUX, BC>): plain, C += A B, sigma' backward (AUX),
 // gathered-combine forward with exactly R = NV in {1, 2} per-edge coefficients, broadcast V with R <= 2 row
 // coefficients (BC, plain or sigma'); no a_idx, coef_idx or planes.
-bool b3_select(const RowGemmP& p, int& nv, bool& aux, bool& bc) {
-    bc = false;
+struct B3Sel {
+    int nv = 0;
+    bool aux = false, bc = false;
+};
+bool b3_select(const RowGemmP& p, B3Sel& sel) {
+    sel.bc = false;
     if (p.precision != IDDGCN_GEMM_BF16X3 || p.a_idx || p.planes) return false;
     if (p.R > 0 && p.v_row_stride == 0 && !p.v_idx) {
         // broadcast V (one row per relation for every output row: dz W_a^T), plain or with the sigma' factor
         if (p.R > 2 || p.coef_idx || p.accumulate || p.act == IDDGCN_ACT_SIGMOID) return false;
-        nv = 0;
-        aux = p.act == IDDGCN_ACT_DSIGMOID;
-        bc = true;
+        sel.nv = 0;
+        sel.aux = p.act == IDDGCN_ACT_DSIGMOID;
+        sel.bc = true;
         return true;
     }
     if (p.R > 0) {
         if (p.R > 2 || p.v_row_stride != 256 || p.coef_idx || p.act == IDDGCN_ACT_DSIGMOID || p.accumulate) return false;
-        nv = p.R;
-        aux = false;
+        sel.nv = p.R;
+        sel.aux = false;
         return true;
     }
     // C += A B (act none): the sigma' kernel's aux slab carries the old C rows (read before the tile is stored)
     if (p.accumulate && p.act != IDDGCN_ACT_NONE) return false;
-    nv = 0;
-    aux = p.act == IDDGCN_ACT_DSIGMOID || p.accumulate;
+    sel.nv = 0;
+    sel.aux = p.act == IDDGCN_ACT_DSIGMOID || p.accumulate;
     return true;
 }
+
+// Which kernel family computes one row GEMM, and that family's variant: the one place where it is decided, for
+// the f32 entries, the bf16-table entry and iddgcn_rowgemm_kernel_id alike.
+struct RowGemmPlan {
+    enum Family { GENERIC, V3, B3, FWD_GATHER8 };
+    Family family = GENERIC;
+    V3Sel v3{};              // family V3
+    B3Sel b3;                // family B3
+    bool bf16_tables = false;
+    int precision = 0;       // RowGemmP::precision of the launch
+    // iddgcn_rowgemm_kernel_id's value (the f32 entries' plans)
+    int id() const {
+        if (bf16_tables) return -1;
+        if (family == B3) return 500 + 10 * b3.nv + (b3.aux ? 1 : 0) + (b3.bc ? 2 : 0);
+        if (family == V3)
+            return 300 + 10 * v3.nv + (v3.aux ? 1 : 0) + (v3.hc ? 2 : 0) + (v3.cw ? 8 : 0) + (v3.split ? 2000 : 0) +
+                   (v3.c4 ? 4000 : 0) + (v3.pl ? 1000 : 0);
+        return 100;
+    }
+};
+RowGemmPlan plan_rowgemm(const RowGemmP& p, int D, bool bf16_tables) {
+    RowGemmPlan plan;
+    plan.bf16_tables = bf16_tables;
+    plan.precision = p.precision;
+    if (bf16_tables) {      // iddgcn_rowgemm_bf16 (D = 256; it has checked the forms it takes)
+        const bool dsig = p.act == IDDGCN_ACT_DSIGMOID;
+        auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+        // config-5 forward form (R = 8, per-edge coefficients, gathered V rows)
+        if (p.R == 8 && p.v_idx && !p.coef_idx && !p.a_idx && !p.b_trans && !dsig && al16(p.A) && al16(p.C) &&
+            al16(p.coef) && al16(p.V) && (p.v_rel_stride & 3) == 0) {
+            plan.family = RowGemmPlan::FWD_GATHER8;
+            return plan;
+        }
+        // gathered-combine forward, sigma' backward, plain
+        plan.family = RowGemmPlan::V3;
+        plan.v3 = {v3_slabs(p.R), dsig, p.R > 0};
+        return plan;
+    }
+    if (p.precision == IDDGCN_GEMM_BF16X3) {
+        if (D == 256 && b3_select(p, plan.b3)) {
+            plan.family = RowGemmPlan::B3;
+            return plan;
+        }
+        plan.precision = IDDGCN_GEMM_EXACT_F32;      // the forms the bf16x3 kernel does not take: exact f32
+    }
+    RowGemmP q = p;
+    q.precision = plan.precision;
+    // D < 256, and the D = 256 forms the v3 kernel does not take: the register-staged kernel (exact f32)
+    if (D == 256 && v3_select(q, plan.v3)) plan.family = RowGemmPlan::V3;
+    return plan;
+}
+
 // ~128 row ranges (a multiple of 8) x 2 column halves: one workgroup per CU, every one resident
-void launch_b3(hipStream_t st, RowGemmP p, int nv, bool aux, bool bc) {
-    const long long nt = ((long long)p.M + rb3::TR - 1) / rb3::TR;
-    long long nr = nt < 128 ? nt : 128;
-    p.tiles_per_block = (int)((nt + nr - 1) / nr);
-    nr = (nt + p.tiles_per_block - 1) / p.tiles_per_block;
-    nr = (nr + 7) / 8 * 8;
+void launch_b3(hipStream_t st, RowGemmP p, const B3Sel& sel) {
+    const TileSplit ts = split_tiles(p.M, rb3::TR, 128);
+    p.tiles_per_block = ts.tiles_per_block;
+    const long long nr = (ts.blocks + 7) / 8 * 8;
     const int n_ranges = (int)nr;
     if (p.accumulate) p.aux = p.C;
     const dim3 g((unsigned)(2 * nr)), blk(512), blk2(1024);      // k-split gathered forward: 16 waves
-    if (bc && aux) hipLaunchKernelGGL((rowgemm256_b3_kernel<0, true, true>), g, blk, 0, st, p, n_ranges);
-    else if (bc) hipLaunchKernelGGL((rowgemm256_b3_kernel<0, false, true>), g, blk, 0, st, p, n_ranges);
-    else if (nv == 1) hipLaunchKernelGGL((rowgemm256_b3_kernel<1, false, false, 2>), g, blk2, 0, st, p, n_ranges);
-    else if (nv == 2) hipLaunchKernelGGL((rowgemm256_b3_kernel<2, false, false, 2>), g, blk2, 0, st, p, n_ranges);
-    else if (aux) hipLaunchKernelGGL((rowgemm256_b3_kernel<0, true>), g, blk, 0, st, p, n_ranges);
+    if (sel.bc && sel.aux) hipLaunchKernelGGL((rowgemm256_b3_kernel<0, true, true>), g, blk, 0, st, p, n_ranges);
+    else if (sel.bc) hipLaunchKernelGGL((rowgemm256_b3_kernel<0, false, true>), g, blk, 0, st, p, n_ranges);
+    else if (sel.nv == 1) hipLaunchKernelGGL((rowgemm256_b3_kernel<1, false, false, 2>), g, blk2, 0, st, p, n_ranges);
+    else if (sel.nv == 2) hipLaunchKernelGGL((rowgemm256_b3_kernel<2, false, false, 2>), g, blk2, 0, st, p, n_ranges);
+    else if (sel.aux) hipLaunchKernelGGL((rowgemm256_b3_kernel<0, true>), g, blk, 0, st, p, n_ranges);
     else hipLaunchKernelGGL((rowgemm256_b3_kernel<0, false>), g, blk, 0, st, p, n_ranges);
 }
 
 // One launch of up to ROWGEMM_BATCH v3 GEMMs of the same variant (blockIdx.y = entry).  The persistent
 // grid is ~256 workgroups in all (one per CU: 131-155 KB of LDS each), shared out over the entries.
+// The if-chains below are the inventory of the v3 instantiations that exist.
 void launch_v3(hipStream_t st, RowGemmBatch& pb, int n, const V3Sel& sel, bool bf = false) {
     // floor: every workgroup of the launch resident at once (ceil gave 7 entries 37 x 7 = 259 > 256 CUs, so three
     // workgroups ran in a second wave and the launch took ~2x)
     const long long per = n > 0 ? (256 / n > 0 ? 256 / n : 1) : 256;
     long long nbmax = 0;
     for (int k = 0; k < n; ++k) {
-        RowGemmP& p = pb.p[k];
-        const long long nt = ((long long)p.M + r3::TR - 1) / r3::TR;
-        long long nb = nt < per ? nt : per;
-        if (nb < 1) nb = 1;
-        p.tiles_per_block = (int)((nt + nb - 1) / nb);
-        if (p.tiles_per_block < 1) p.tiles_per_block = 1;
-        nb = (nt + p.tiles_per_block - 1) / p.tiles_per_block;
-        if (nb > nbmax) nbmax = nb;
+        const TileSplit ts = split_tiles(pb.p[k].M, r3::TR, per);
+        pb.p[k].tiles_per_block = ts.tiles_per_block;
+        if (ts.blocks > nbmax) nbmax = ts.blocks;
     }
     if (nbmax == 0) return;
     const dim3 g((unsigned)nbmax, (unsigned)n), blk(512);
+#define V3K(...) hipLaunchKernelGGL((rowgemm256_v3_kernel<__VA_ARGS__>), g, blk, 0, st, pb)
     if (bf) {      // bf16 edge tables: gathered-combine forward, sigma' backward, plain
-#define V3B(NV, AUX, HC)                                                                                         \
-    do {                                                                                                          \
-        if (pb.p[0].precision == IDDGCN_GEMM_BF16)                                                                \
-            hipLaunchKernelGGL((rowgemm256_v3_kernel<NV, AUX, HC, true, false, true, false, false, true>), g, blk, 0, st, pb); \
-        else hipLaunchKernelGGL((rowgemm256_v3_kernel<NV, AUX, HC, true, false, true>), g, blk, 0, st, pb);        \
+#define V3B(NV, AUX, HC)                                                                      \
+    do {                                                                                       \
+        if (pb.p[0].precision == IDDGCN_GEMM_BF16) V3K(NV, AUX, HC, true, false, true, false, false, true); \
+        else V3K(NV, AUX, HC, true, false, true);                                              \
     } while (0)
         if (sel.nv == 1) V3B(1, false, true);
         else if (sel.nv == 2) V3B(2, false, true);
@@ -4740,70 +4874,30 @@ void launch_v3(hipStream_t st, RowGemmBatch& pb, int n, const V3Sel& sel, bool b
 #undef V3B
         return;
     }
-    const bool x3 = sel.split;
-#define V3L(NV, AUX, HC)                                                                        \
-    {                                                                                           \
-        if (x3) hipLaunchKernelGGL((rowgemm256_v3_kernel<NV, AUX, HC, true>), g, blk, 0, st, pb); \
-        else hipLaunchKernelGGL((rowgemm256_v3_kernel<NV, AUX, HC, false>), g, blk, 0, st, pb);   \
-    }
-#define V3W(AUX)                                                                                     \
-    {                                                                                                \
-        if (x3) hipLaunchKernelGGL((rowgemm256_v3_kernel<0, AUX, true, true, true>), g, blk, 0, st, pb); \
-        else hipLaunchKernelGGL((rowgemm256_v3_kernel<0, AUX, true, false, true>), g, blk, 0, st, pb);   \
-    }
+    // exact f32 or split fp16 operands (template X3), CW: broadcast V with R > 2 coefficients
+#define V3L(NV, AUX, HC, CW)                       \
+    do {                                           \
+        if (sel.split) V3K(NV, AUX, HC, true, CW); \
+        else V3K(NV, AUX, HC, false, CW);          \
+    } while (0)
     if (sel.c4) {           // check_rowgemm / v3_select: the plain f32 form
-        hipLaunchKernelGGL((rowgemm256_v3_kernel<0, false, false, false, false, false, false, true>), g, blk, 0, st, pb);
+        V3K(0, false, false, false, false, false, false, true);
     } else if (sel.pl) {    // check_rowgemm: split mode
-        if (sel.nv == 1) hipLaunchKernelGGL((rowgemm256_v3_kernel<1, false, true, true, false, false, true>), g, blk, 0, st, pb);
-        else if (sel.nv == 2) hipLaunchKernelGGL((rowgemm256_v3_kernel<2, false, true, true, false, false, true>), g, blk, 0, st, pb);
-        else hipLaunchKernelGGL((rowgemm256_v3_kernel<0, true, false, true, false, false, true>), g, blk, 0, st, pb);
-    } else if (sel.nv == 1) V3L(1, false, true)
-    else if (sel.nv == 2) V3L(2, false, true)
-    else if (sel.nv == 4) V3L(4, false, true)
-    else if (sel.nv == 8) V3L(8, false, true)
-    else if (sel.hc && sel.cw) {
-        if (sel.aux) V3W(true)
-        else V3W(false)
-    } else if (sel.hc && sel.aux) V3L(0, true, true)
-    else if (sel.hc) V3L(0, false, true)
-    else if (sel.aux) V3L(0, true, false)
-    else V3L(0, false, false)
+        if (sel.nv == 1) V3K(1, false, true, true, false, false, true);
+        else if (sel.nv == 2) V3K(2, false, true, true, false, false, true);
+        else V3K(0, true, false, true, false, false, true);
+    } else if (sel.nv == 1) V3L(1, false, true, false);
+    else if (sel.nv == 2) V3L(2, false, true, false);
+    else if (sel.nv == 4) V3L(4, false, true, false);
+    else if (sel.nv == 8) V3L(8, false, true, false);
+    else if (sel.hc && sel.cw && sel.aux) V3L(0, true, true, true);
+    else if (sel.hc && sel.cw) V3L(0, false, true, true);
+    else if (sel.hc && sel.aux) V3L(0, true, true, false);
+    else if (sel.hc) V3L(0, false, true, false);
+    else if (sel.aux) V3L(0, true, false, false);
+    else V3L(0, false, false, false);
 #undef V3L
-#undef V3W
-}
-
-// the run combine (D = 256) writing bf16 rows (BF) or planes rows (PL)
-template <bool BF, bool PL>
-int run_combine_out(void* stream, int M, int d, int R, const float* Y, const int* idx, const float* coef,
-                    const float* V, long long v_rel_stride, void* out) {
-    if (d != 256) return IDDGCN_E_BAD_DIM;
-    if (R < 0 || R > MAX_R) return IDDGCN_E_BAD_REL;
-    if (M < 0 || !Y || !idx || !out || (R > 0 && (!coef || !V))) return IDDGCN_E_BAD_ARG;
-    if (M == 0) return 0;
-    const long long nchunk = ((long long)M + RC_CH - 1) / RC_CH;
-    long long nb = (nchunk + 3) / 4;
-    if (nb > 2048) nb = 2048;
-    hipStream_t st = (hipStream_t)stream;
-    float* o = (float*)out;
-#define RCB(RR) hipLaunchKernelGGL((run_combine256_kernel<RR, BF, PL>), dim3((unsigned)nb), dim3(256), 0, st, M, Y, idx, coef, V, v_rel_stride, o)
-    switch (R) {
-        case 0: RCB(0); break;
-        case 1: RCB(1); break;
-        case 2: RCB(2); break;
-        case 3: RCB(3); break;
-        case 4: RCB(4); break;
-        case 5: RCB(5); break;
-        case 6: RCB(6); break;
-        case 7: RCB(7); break;
-        default: RCB(8); break;
-    }
-#undef RCB
-    return launch_status();
-}
-
-inline unsigned grid_for(long long rows, int lpr) {
-    const long long threads = rows * lpr;
-    return (unsigned)((threads + 255) / 256);
+#undef V3K
 }
 
 // ---------------------------------------------------------------------------
@@ -5106,14 +5200,75 @@ __global__ __launch_bounds__(512) void fwd_gather8_bf16_kernel(RowGemmP p) {
     for (int q = 0; q < 8; ++q) finish(t_end - 1, q);
 }
 
+
 // config-5 forward form (R = 8, per-edge coefficients, gathered V rows, bf16 A / C): one persistent workgroup per CU
 void launch_fwd_gather8(hipStream_t st, RowGemmP p) {
-    const long long ntiles = ((long long)p.M + fg8::TR - 1) / fg8::TR;
-    long long nb = ntiles < 256 ? ntiles : 256;
-    p.tiles_per_block = (int)((ntiles + nb - 1) / nb);
-    nb = (ntiles + p.tiles_per_block - 1) / p.tiles_per_block;
-    if (p.precision == IDDGCN_GEMM_BF16) hipLaunchKernelGGL(fwd_gather8_bf16_kernel<false>, dim3((unsigned)nb), dim3(512), 0, st, p);
-    else hipLaunchKernelGGL(fwd_gather8_bf16_kernel<true>, dim3((unsigned)nb), dim3(512), 0, st, p);
+    const TileSplit ts = split_tiles(p.M, fg8::TR, 256);
+    p.tiles_per_block = ts.tiles_per_block;
+    const dim3 g((unsigned)ts.blocks), blk(512);
+    if (p.precision == IDDGCN_GEMM_BF16) hipLaunchKernelGGL(fwd_gather8_bf16_kernel<false>, g, blk, 0, st, p);
+    else hipLaunchKernelGGL(fwd_gather8_bf16_kernel<true>, g, blk, 0, st, p);
+}
+
+// the run combine (D = 256): fp32 rows, bf16 rows (BF) or planes rows (PL)
+template <bool BF, bool PL>
+void launch_run_combine(hipStream_t st, int M, int R, const float* Y, const int* idx, const float* coef,
+                        const float* V, long long v_rel_stride, float* out) {
+    const long long nchunk = ((long long)M + RC_CH - 1) / RC_CH;
+    long long nb = (nchunk + 3) / 4;
+    if (nb > 2048) nb = 2048;
+    for_rel<0>(R, [&](auto Rc) {
+        hipLaunchKernelGGL((run_combine256_kernel<decltype(Rc)::value, BF, PL>), dim3((unsigned)nb), dim3(256), 0, st,
+                           M, Y, idx, coef, V, v_rel_stride, out);
+    });
+}
+template <bool BF, bool PL>
+int run_combine_out(void* stream, int M, int d, int R, const float* Y, const int* idx, const float* coef,
+                    const float* V, long long v_rel_stride, void* out) {
+    if (d != 256) return IDDGCN_E_BAD_DIM;
+    if (R < 0 || R > MAX_R) return IDDGCN_E_BAD_REL;
+    if (M < 0 || !Y || !idx || !out || (R > 0 && (!coef || !V))) return IDDGCN_E_BAD_ARG;
+    if (M == 0) return 0;
+    launch_run_combine<BF, PL>((hipStream_t)stream, M, R, Y, idx, coef, V, v_rel_stride, (float*)out);
+    return launch_status();
+}
+
+// the fused sigma' + dS passes (D = 256): M rows in tile_rows tiles over iddgcn_sigma_tn_ranges(M) row ranges x 2
+// column halves; launch(grid, tiles per range, ranges) starts the entry's kernel
+template <class Launch>
+int sigma_tn(hipStream_t st, long long M, int d, bool precision_ok, const void* dO, const void* X, const float* S,
+             float* slab, long long slab_floats, float* dS, int tile_rows, Launch&& launch) {
+    if (d != 256) return IDDGCN_E_BAD_DIM;
+    if (!precision_ok) return IDDGCN_E_BAD_ARG;
+    if (M < 0 || !S || !slab || !dS || (M > 0 && (!dO || !X))) return IDDGCN_E_BAD_ARG;
+    if (((uintptr_t)dO & 15) || ((uintptr_t)X & 15)) return IDDGCN_E_BAD_ARG;
+    const long long nt = (M + tile_rows - 1) / tile_rows;
+    const int nr = iddgcn_sigma_tn_ranges(M);
+    const long long tpb = nt > 0 ? (nt + nr - 1) / nr : 1;
+    if (slab_floats < nr * (long long)d * d) return IDDGCN_E_BAD_ARG;
+    launch(dim3((unsigned)(2 * nr)), (int)tpb, nr);
+    return reduce_tn_slabs(st, nr, d, slab, dS, 0);
+}
+
+// argument checks shared by the fp32 and bf16 DistMult entries (width_ok: the entry's own width rule)
+int check_distmult(bool width_ok, long long T, int R, int n_blocks, const void* Xh, const void* h_idx, const void* Xt,
+                   const void* r_idx, const void* rel, const void* y, const void* ds_out, const void* do_out,
+                   const void* drel_slab, const void* loss_slab) {
+    if (!width_ok) return IDDGCN_E_BAD_DIM;
+    if (R < 1 || R > MAX_R) return IDDGCN_E_BAD_REL;
+    if (T < 0 || n_blocks < 1 || !Xh || !h_idx || !Xt || !r_idx || !rel) return IDDGCN_E_BAD_ARG;
+    if (y && (!ds_out || !do_out || !drel_slab || !loss_slab)) return IDDGCN_E_BAD_ARG;
+    return 0;
+}
+int check_distmult_heads(bool width_ok, int n_nodes, int R, int n_blocks, const void* seg_ptr, const void* perm,
+                         const void* Xh, const void* Xt, const void* r_idx, const void* rel, const void* do_out,
+                         const void* dXh, const void* drel_slab, const void* loss_slab) {
+    if (!width_ok) return IDDGCN_E_BAD_DIM;
+    if (R < 1 || R > MAX_R) return IDDGCN_E_BAD_REL;
+    if (n_nodes < 0 || n_blocks < 1 || !seg_ptr || !perm || !Xh || !Xt || !r_idx || !rel || !do_out || !dXh ||
+        !drel_slab || !loss_slab)
+        return IDDGCN_E_BAD_ARG;
+    return 0;
 }
 
 // the config-5 tail reduction on MFMAs (tail_seg_mfma8_kernel), with or without the head chain's node terms
@@ -5149,14 +5304,10 @@ int iddgcn_spmm_csr_f32(void* stream, int n_seg, int n_rows, int d, const int* r
     if (rows == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = grid_for(rows, d / 4);
-#define SPMM(DD) hipLaunchKernelGGL(spmm_csr_kernel<DD>, dim3(grid), dim3(256), 0, st, n_seg, n_rows, row_ptr, col, vals, X, Y, accumulate)
-    switch (d) {
-        case 32: SPMM(32); break;
-        case 64: SPMM(64); break;
-        case 128: SPMM(128); break;
-        default: SPMM(256); break;
-    }
-#undef SPMM
+    for_width(d, [&](auto D) {
+        hipLaunchKernelGGL(spmm_csr_kernel<decltype(D)::value>, dim3(grid), dim3(256), 0, st, n_seg, n_rows, row_ptr,
+                           col, vals, X, Y, accumulate);
+    });
     return launch_status();
 }
 
@@ -5168,139 +5319,104 @@ int iddgcn_sddmm_csr_f32(void* stream, int n_seg, int n_rows, int d, const int* 
     if (rows == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = grid_for(rows, d / 4);
-#define SDK(DD) hipLaunchKernelGGL(sddmm_csr_kernel<DD>, dim3(grid), dim3(256), 0, st, n_seg, n_rows, row_ptr, col, G, X, out)
-    switch (d) {
-        case 32: SDK(32); break;
-        case 64: SDK(64); break;
-        case 128: SDK(128); break;
-        default: SDK(256); break;
-    }
-#undef SDK
+    for_width(d, [&](auto D) {
+        hipLaunchKernelGGL(sddmm_csr_kernel<decltype(D)::value>, dim3(grid), dim3(256), 0, st, n_seg, n_rows, row_ptr,
+                           col, G, X, out);
+    });
     return launch_status();
 }
+
+}  // extern "C"
+
+// The row-GEMM launchers stand here, not with the other host code above, because the compiler emits the kernel
+// templates in the order this file first names them: rowgemm_kernel<D> after the CSR kernels, as it always was.
+namespace {
+
+// The register-staged kernel (every width, exact f32): n entries of width d in one launch (blockIdx.y = entry),
+// persistent workgroups up to the width's cap.  False: no entry has a row, nothing launched.
+bool launch_generic(hipStream_t st, RowGemmBatch& pb, int n, int d) {
+    const long long cap = d == 256 ? 256 : d == 128 ? 1024 : 2048;
+    long long nbmax = 0;
+    for_width(d, [&](auto Dc) {
+        constexpr int D = decltype(Dc)::value;
+        for (int k = 0; k < n; ++k) {
+            const TileSplit ts = split_tiles(pb.p[k].M, RG<D>::TR, cap);
+            pb.p[k].tiles_per_block = ts.tiles_per_block;
+            if (ts.blocks > nbmax) nbmax = ts.blocks;
+        }
+        if (nbmax == 0) return;
+        hipLaunchKernelGGL(rowgemm_kernel<D>, dim3((unsigned)nbmax, (unsigned)n), dim3(RG<D>::NW * 64), 0, st, pb);
+    });
+    return nbmax != 0;
+}
+
+// one row GEMM (M > 0) on the kernel its plan names
+void launch_rowgemm(hipStream_t st, RowGemmP p, int D, const RowGemmPlan& plan) {
+    p.precision = plan.precision;
+    if (plan.family == RowGemmPlan::B3) return launch_b3(st, p, plan.b3);
+    if (plan.family == RowGemmPlan::FWD_GATHER8) return launch_fwd_gather8(st, p);
+    RowGemmBatch pb;
+    pb.p[0] = p;
+    if (plan.family == RowGemmPlan::V3) launch_v3(st, pb, 1, plan.v3, plan.bf16_tables);
+    else launch_generic(st, pb, 1, D);
+}
+
+}  // namespace
+
+extern "C" {
 
 int iddgcn_rowgemm_f32(void* stream, const iddgcn_rowgemm_t* a) {
     if (!a) return IDDGCN_E_BAD_ARG;
     if (const int rc = check_rowgemm(*a)) return rc;
     if (a->M == 0) return 0;                 // nothing to do (an empty C may have a null pointer)
-    RowGemmP p = to_p(*a);
-    hipStream_t st = (hipStream_t)stream;
-    if (p.precision == IDDGCN_GEMM_BF16X3) {
-        int nv;
-        bool aux, bc;
-        if (a->D == 256 && b3_select(p, nv, aux, bc)) {
-            launch_b3(st, p, nv, aux, bc);
-            return launch_status();
-        }
-        p.precision = IDDGCN_GEMM_EXACT_F32;      // the forms the bf16x3 kernel does not take: exact f32
-    }
-    V3Sel sel;
-    if (a->D == 256 && v3_select(p, sel)) {
-        RowGemmBatch pb;
-        pb.p[0] = p;
-        launch_v3(st, pb, 1, sel);
-        return launch_status();
-    }
-    // D < 256, and the D = 256 forms the v3 kernel does not take: the register-staged kernel (exact f32)
-#define RGEMM(DD, MAXB)                                                                         \
-    {                                                                                           \
-        const long long nt = ((long long)p.M + RG<DD>::TR - 1) / RG<DD>::TR;                    \
-        long long nb = nt < (MAXB) ? nt : (MAXB);                                               \
-        p.tiles_per_block = (int)((nt + nb - 1) / nb);                                          \
-        nb = (nt + p.tiles_per_block - 1) / p.tiles_per_block;                                  \
-        RowGemmBatch pb;                                                                        \
-        pb.p[0] = p;                                                                            \
-        hipLaunchKernelGGL(rowgemm_kernel<DD>, dim3((unsigned)nb), dim3(RG<DD>::NW * 64), 0, st, pb); \
-    }
-    switch (a->D) {
-        case 32: RGEMM(32, 2048); break;
-        case 64: RGEMM(64, 2048); break;
-        case 128: RGEMM(128, 1024); break;
-        default: RGEMM(256, 256); break;
-    }
-#undef RGEMM
+    const RowGemmP p = to_p(*a);
+    launch_rowgemm((hipStream_t)stream, p, a->D, plan_rowgemm(p, a->D, false));
     return launch_status();
 }
 
 int iddgcn_rowgemm_kernel_id(const iddgcn_rowgemm_t* a) {
     if (!a || !dim_ok(a->D)) return -1;
-    RowGemmP p = to_p(*a);
-    if (p.precision == IDDGCN_GEMM_BF16X3) {
-        int nv;
-        bool aux, bc;
-        if (a->D == 256 && b3_select(p, nv, aux, bc)) return 500 + 10 * nv + (aux ? 1 : 0) + (bc ? 2 : 0);
-        p.precision = IDDGCN_GEMM_EXACT_F32;
-    }
-    V3Sel sel;
-    if (a->D == 256 && v3_select(p, sel))
-        return 300 + 10 * sel.nv + (sel.aux ? 1 : 0) + (sel.hc ? 2 : 0) + (sel.cw ? 8 : 0) + (sel.split ? 2000 : 0) +
-               (sel.c4 ? 4000 : 0) + (sel.pl ? 1000 : 0);
-    return 100;
+    return plan_rowgemm(to_p(*a), a->D, false).id();
 }
 
 int iddgcn_rowgemm_batched_f32(void* stream, const iddgcn_rowgemm_t* a, int n) {
     if (!a || n < 0 || n > ROWGEMM_BATCH) return IDDGCN_E_BAD_ARG;
     if (n == 0) return 0;
-    bool one_launch = a[0].D != 256;
     for (int k = 0; k < n; ++k) {
         if (!dim_ok(a[k].D) || a[k].D != a[0].D) return IDDGCN_E_BAD_DIM;
         if (const int rc = check_rowgemm(a[k])) return rc;
     }
-    for (int k = 0; k < n && !one_launch; ++k)
-        if (a[k].precision == IDDGCN_GEMM_BF16X3) {      // D = 256 bf16x3: one call per entry
-            for (int j = 0; j < n; ++j) {
-                const int rc = iddgcn_rowgemm_f32(stream, a + j);
-                if (rc) return rc;
-            }
-            return 0;
-        }
-    if (!one_launch) {          // D = 256: one v3 launch when every entry maps to the same variant
-        RowGemmBatch pb;
-        V3Sel sel0{}, sel{};
-        bool same = true;
-        int m = 0;
-        for (int k = 0; k < n && same; ++k) {
-            if (a[k].M == 0) continue;
-            RowGemmP& p = pb.p[m];
-            p = to_p(a[k]);
-            if (!v3_select(p, sel)) same = false;
-            else if (m == 0) sel0 = sel;
-            else same = sel.same(sel0);
-            ++m;
-        }
-        if (same) {
-            if (m > 0) launch_v3((hipStream_t)stream, pb, m, sel0);
-            return launch_status();
-        }
-        for (int k = 0; k < n; ++k) {
-            const int rc = iddgcn_rowgemm_f32(stream, a + k);
-            if (rc) return rc;
-        }
-        return 0;
-    }
-    RowGemmBatch pb;
-    long long nbmax = 0;
-    const int d = a[0].D;
-    const int tr = d == 32 ? RG<32>::TR : d == 64 ? RG<64>::TR : RG<128>::TR;
-    const long long maxb = d == 128 ? 1024 : 2048;
-    for (int k = 0; k < n; ++k) {
-        RowGemmP& p = pb.p[k];
-        p = to_p(a[k]);
-        const long long nt = ((long long)p.M + tr - 1) / tr;
-        long long nb = nt < maxb ? nt : maxb;
-        p.tiles_per_block = nb > 0 ? (int)((nt + nb - 1) / nb) : 1;
-        nb = nb > 0 ? (nt + p.tiles_per_block - 1) / p.tiles_per_block : 0;
-        if (nb > nbmax) nbmax = nb;
-    }
-    if (nbmax == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 g((unsigned)nbmax, (unsigned)n);
-    switch (d) {
-        case 32: hipLaunchKernelGGL(rowgemm_kernel<32>, g, dim3(RG<32>::NW * 64), 0, st, pb); break;
-        case 64: hipLaunchKernelGGL(rowgemm_kernel<64>, g, dim3(RG<64>::NW * 64), 0, st, pb); break;
-        default: hipLaunchKernelGGL(rowgemm_kernel<128>, g, dim3(RG<128>::NW * 64), 0, st, pb); break;
+    RowGemmBatch pb;
+    if (a[0].D != 256) {        // one launch of the register-staged kernel
+        for (int k = 0; k < n; ++k) pb.p[k] = to_p(a[k]);
+        return launch_generic(st, pb, n, a[0].D) ? launch_status() : 0;
     }
-    return launch_status();
+    // D = 256: one v3 launch when every entry with rows maps to the same v3 variant (bf16x3: one launch per entry)
+    V3Sel sel0{};
+    bool one_launch = true;
+    int m = 0;
+    for (int k = 0; k < n && one_launch; ++k) {
+        const RowGemmP p = to_p(a[k]);
+        if (p.precision == IDDGCN_GEMM_BF16X3) one_launch = false;
+        else if (p.M != 0) {
+            const RowGemmPlan plan = plan_rowgemm(p, 256, false);
+            one_launch = plan.family == RowGemmPlan::V3 && (m == 0 || plan.v3.same(sel0));
+            if (m == 0) sel0 = plan.v3;
+            pb.p[m++] = p;
+        }
+    }
+    if (one_launch) {
+        if (m > 0) launch_v3(st, pb, m, sel0);
+        return launch_status();
+    }
+    for (int k = 0; k < n; ++k) {
+        if (a[k].M == 0) continue;
+        const RowGemmP p = to_p(a[k]);
+        launch_rowgemm(st, p, 256, plan_rowgemm(p, 256, false));
+        if (const int rc = launch_status()) return rc;
+    }
+    return 0;
 }
 
 int iddgcn_gemm_tn_blocks(long long M, int d) {
@@ -5314,38 +5430,28 @@ int iddgcn_gemm_tn_f32(void* stream, long long M, int d, const float* A, const f
                        float* C, int accumulate, int precision) {
     if (!dim_ok(d)) return IDDGCN_E_BAD_DIM;
     if (M < 0 || n_blocks < 1 || !A || !B || !slab || !C) return IDDGCN_E_BAD_ARG;
-    if (precision != IDDGCN_GEMM_EXACT_F32 && precision != IDDGCN_GEMM_SPLIT_F16 && precision != IDDGCN_GEMM_BF16X3)
-        return IDDGCN_E_BAD_ARG;
+    if (!tn_precision_ok(precision)) return IDDGCN_E_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    long long rpb = (M + n_blocks - 1) / n_blocks;
-    rpb = ((rpb + 31) / 32) * 32;
-    if (rpb < 32) rpb = 32;
-#define TNK(DD) hipLaunchKernelGGL(gemm_tn_kernel<DD>, dim3(n_blocks), dim3(TN<DD>::NW * 64), 0, st, M, rpb, A, B, slab)
+    const long long rpb = tn_rows_per_block(M, n_blocks);
     if (d == 256 && precision == IDDGCN_GEMM_BF16X3) {
         hipLaunchKernelGGL(gemm_tn256_b3_kernel, dim3(n_blocks), dim3(512), 0, st, M, rpb, A, B, slab, TnBatch{});
     } else if (d == 256 && precision == IDDGCN_GEMM_SPLIT_F16) {
         hipLaunchKernelGGL(gemm_tn256_x3_kernel<>, dim3(n_blocks), dim3(512), 0, st, M, rpb, A, B, slab, TnBatch{});
     } else if (d == 256) {
         hipLaunchKernelGGL(gemm_tn256_dma_kernel, dim3(n_blocks), dim3(512), 0, st, M, rpb, A, B, slab);
-    } else switch (d) {
-        case 32: TNK(32); break;
-        case 64: TNK(64); break;
-        default: TNK(128); break;
+    } else switch (d) {         // the generic kernel exists below 256 only
+        case 32: hipLaunchKernelGGL(gemm_tn_kernel<32>, dim3(n_blocks), dim3(TN<32>::NW * 64), 0, st, M, rpb, A, B, slab); break;
+        case 64: hipLaunchKernelGGL(gemm_tn_kernel<64>, dim3(n_blocks), dim3(TN<64>::NW * 64), 0, st, M, rpb, A, B, slab); break;
+        default: hipLaunchKernelGGL(gemm_tn_kernel<128>, dim3(n_blocks), dim3(TN<128>::NW * 64), 0, st, M, rpb, A, B, slab); break;
     }
-#undef TNK
-    int rc = launch_status();
-    if (rc) return rc;
-    const long long n = (long long)d * d;
-    launch_reduce_slabs(st, n_blocks, n, slab, C, accumulate, 1.0f);
-    return launch_status();
+    return reduce_tn_slabs(st, n_blocks, d, slab, C, accumulate);
 }
 
 int iddgcn_gemm_tn_batched_f32(void* stream, int d, const iddgcn_tn_t* e, int n, float* slab, long long slab_floats,
                                int precision) {
     if (!dim_ok(d)) return IDDGCN_E_BAD_DIM;
     if (n < 0 || n > IDDGCN_TN_BATCH || (n > 0 && (!e || !slab))) return IDDGCN_E_BAD_ARG;
-    if (precision != IDDGCN_GEMM_EXACT_F32 && precision != IDDGCN_GEMM_SPLIT_F16 && precision != IDDGCN_GEMM_BF16X3)
-        return IDDGCN_E_BAD_ARG;
+    if (!tn_precision_ok(precision)) return IDDGCN_E_BAD_ARG;
     for (int k = 0; k < n; ++k)
         if (e[k].M < 0 || (e[k].M > 0 && (!e[k].A || !e[k].B)) || !e[k].C) return IDDGCN_E_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -5378,14 +5484,11 @@ int iddgcn_gemm_tn_batched_f32(void* stream, int d, const iddgcn_tn_t* e, int n,
         long long nb = 256 / n;                    // every workgroup of the launch resident at once
         if (nb > tiles) nb = tiles;
         if (nb < 1) nb = 1;
-        long long rpb = (e[k].M + nb - 1) / nb;
-        rpb = ((rpb + 31) / 32) * 32;
-        if (rpb < 32) rpb = 32;
         nbk[k] = (int)nb;
         tb.nb[k] = (int)nb;
         if ((unsigned)nb > nbmax) nbmax = (unsigned)nb;
         tb.M[k] = e[k].M;
-        tb.rpb[k] = rpb;
+        tb.rpb[k] = tn_rows_per_block(e[k].M, nb);
         tb.A[k] = e[k].A;
         tb.B[k] = e[k].B;
         tb.slab[k] = slab + off;
@@ -5410,16 +5513,9 @@ int iddgcn_gemm_tn_planes_f32(void* stream, long long M, int d, const void* A, c
     if (d != 256) return IDDGCN_E_BAD_DIM;
     if (M < 0 || n_blocks < 1 || !A || !B || !slab || !C) return IDDGCN_E_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    long long rpb = (M + n_blocks - 1) / n_blocks;
-    rpb = ((rpb + 31) / 32) * 32;
-    if (rpb < 32) rpb = 32;
-    hipLaunchKernelGGL((gemm_tn256_x3_kernel<true>), dim3(n_blocks), dim3(512), 0, st, M, rpb, (const float*)A, B, slab,
-                       TnBatch{});
-    int rc = launch_status();
-    if (rc) return rc;
-    const long long n = (long long)d * d;
-    launch_reduce_slabs(st, n_blocks, n, slab, C, accumulate, 1.0f);
-    return launch_status();
+    hipLaunchKernelGGL((gemm_tn256_x3_kernel<true>), dim3(n_blocks), dim3(512), 0, st, M, tn_rows_per_block(M, n_blocks),
+                       (const float*)A, B, slab, TnBatch{});
+    return reduce_tn_slabs(st, n_blocks, d, slab, C, accumulate);
 }
 
 int iddgcn_gemm_tn_narrow_blocks(long long M) {
@@ -5435,14 +5531,10 @@ int iddgcn_gemm_tn_narrow_f32(void* stream, long long M, int d, int R, const flo
     if (M < 0 || n_blocks < 1 || !A || !dz || !slab || !dWa || !dba) return IDDGCN_E_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     const long long rpb = (M + n_blocks - 1) / n_blocks;
-#define NK(DD) hipLaunchKernelGGL(gemm_tn_narrow_kernel<DD>, dim3(n_blocks), dim3(DD), 0, st, M, rpb, R, A, dz, slab)
-    switch (d) {
-        case 32: NK(32); break;
-        case 64: NK(64); break;
-        case 128: NK(128); break;
-        default: NK(256); break;
-    }
-#undef NK
+    for_width(d, [&](auto Dc) {
+        constexpr int D = decltype(Dc)::value;
+        hipLaunchKernelGGL(gemm_tn_narrow_kernel<D>, dim3(n_blocks), dim3(D), 0, st, M, rpb, R, A, dz, slab);
+    });
     int rc = launch_status();
     if (rc) return rc;
     // slab rows are [(D+1)*R]; reduce the weight part and the bias part separately
@@ -5470,14 +5562,10 @@ int iddgcn_alpha_fwd_f32(void* stream, int M, int d, int R, const float* X, cons
     hipStream_t st = (hipStream_t)stream;
     unsigned grid = grid_for(M, d / 4);
     if (grid > 2048) grid = 2048;            // persistent: W_alpha loaded once per lane group
-#define AK(DD) hipLaunchKernelGGL(alpha_kernel<DD>, dim3(grid), dim3(256), 0, st, M, R, X, x_idx, Wa, ba, S_out, W_out)
-    switch (d) {
-        case 32: AK(32); break;
-        case 64: AK(64); break;
-        case 128: AK(128); break;
-        default: AK(256); break;
-    }
-#undef AK
+    for_width(d, [&](auto D) {
+        hipLaunchKernelGGL(alpha_kernel<decltype(D)::value>, dim3(grid), dim3(256), 0, st, M, R, X, x_idx, Wa, ba,
+                           S_out, W_out);
+    });
     return launch_status();
 }
 
@@ -5489,47 +5577,17 @@ int iddgcn_combine_f32(void* stream, int M, int d, int R, const float* Y, const 
     if (M == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     if (d == 256 && y_idx && y_idx == v_idx && !coef_idx) {
-        const long long nchunk = ((long long)M + RC_CH - 1) / RC_CH;
-        long long nb = (nchunk + 3) / 4;
-        if (nb > 2048) nb = 2048;
-#define RCK(RR) hipLaunchKernelGGL((run_combine256_kernel<RR>), dim3((unsigned)nb), dim3(256), 0, st, M, Y, y_idx, coef, V, v_rel_stride, out)
-        switch (R) {
-            case 0: RCK(0); break;
-            case 1: RCK(1); break;
-            case 2: RCK(2); break;
-            case 3: RCK(3); break;
-            case 4: RCK(4); break;
-            case 5: RCK(5); break;
-            case 6: RCK(6); break;
-            case 7: RCK(7); break;
-            default: RCK(8); break;
-        }
-#undef RCK
+        launch_run_combine<false, false>(st, M, R, Y, y_idx, coef, V, v_rel_stride, out);
         return launch_status();
     }
     const long long nbatch = ((long long)M + (256 / (d / 4)) * CU_ROWS - 1) / ((256 / (d / 4)) * CU_ROWS);
     const unsigned grid = (unsigned)(nbatch < CU_BLOCKS ? nbatch : CU_BLOCKS);
-#define CK(DD, RR) hipLaunchKernelGGL((combine_kernel<DD, RR>), dim3(grid), dim3(256), 0, st, M, Y, y_idx, coef, coef_idx, V, v_idx, v_rel_stride, out)
-#define CKR(DD)                    \
-    switch (R) {                   \
-        case 0: CK(DD, 0); break;  \
-        case 1: CK(DD, 1); break;  \
-        case 2: CK(DD, 2); break;  \
-        case 3: CK(DD, 3); break;  \
-        case 4: CK(DD, 4); break;  \
-        case 5: CK(DD, 5); break;  \
-        case 6: CK(DD, 6); break;  \
-        case 7: CK(DD, 7); break;  \
-        default: CK(DD, 8); break; \
-    }
-    switch (d) {
-        case 32: CKR(32); break;
-        case 64: CKR(64); break;
-        case 128: CKR(128); break;
-        default: CKR(256); break;
-    }
-#undef CKR
-#undef CK
+    for_width(d, [&](auto D) {
+        for_rel<0>(R, [&](auto Rc) {
+            hipLaunchKernelGGL((combine_kernel<decltype(D)::value, decltype(Rc)::value>), dim3(grid), dim3(256), 0, st, M,
+                               Y, y_idx, coef, coef_idx, V, v_idx, v_rel_stride, out);
+        });
+    });
     return launch_status();
 }
 
@@ -5543,20 +5601,15 @@ int iddgcn_distmult_bce_f32(void* stream, long long T, int d, int R, const float
                             const float* Xt, const int* t_idx, const int* r_idx, const float* rel, const float* y,
                             float scale, float* p_out, float* s_out, float* ds_out, float* do_out,
                             float* drel_slab, float* loss_slab, int n_blocks) {
-    if (!dim_ok(d)) return IDDGCN_E_BAD_DIM;
-    if (R < 1 || R > MAX_R) return IDDGCN_E_BAD_REL;
-    if (T < 0 || n_blocks < 1 || !Xh || !h_idx || !Xt || !r_idx || !rel) return IDDGCN_E_BAD_ARG;
-    if (y && (!ds_out || !do_out || !drel_slab || !loss_slab)) return IDDGCN_E_BAD_ARG;
+    if (const int rc = check_distmult(dim_ok(d), T, R, n_blocks, Xh, h_idx, Xt, r_idx, rel, y, ds_out, do_out,
+                                      drel_slab, loss_slab))
+        return rc;
     if (T == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-#define DK(DD) hipLaunchKernelGGL(distmult_kernel<DD>, dim3(n_blocks), dim3(256), 0, st, T, R, Xh, h_idx, Xt, t_idx, r_idx, rel, y, scale, p_out, s_out, ds_out, do_out, drel_slab, loss_slab)
-    switch (d) {
-        case 32: DK(32); break;
-        case 64: DK(64); break;
-        case 128: DK(128); break;
-        default: DK(256); break;
-    }
-#undef DK
+    for_width(d, [&](auto D) {
+        hipLaunchKernelGGL(distmult_kernel<decltype(D)::value>, dim3(n_blocks), dim3(256), 0, st, T, R, Xh, h_idx, Xt,
+                           t_idx, r_idx, rel, y, scale, p_out, s_out, ds_out, do_out, drel_slab, loss_slab);
+    });
     return launch_status();
 }
 
@@ -5564,28 +5617,17 @@ int iddgcn_distmult_bce_heads_f32(void* stream, int n_nodes, int d, int R, const
                                   const float* Xh, const float* Xt, const int* r_idx, const float* rel,
                                   const float* y, float scale, float* p_out, float* s_out, float* ds_out,
                                   float* do_out, float* dXh, float* drel_slab, float* loss_slab, int n_blocks) {
-    if (!dim_ok(d)) return IDDGCN_E_BAD_DIM;
-    if (R < 1 || R > MAX_R) return IDDGCN_E_BAD_REL;
-    if (n_nodes < 0 || n_blocks < 1 || !seg_ptr || !perm || !Xh || !Xt || !r_idx || !rel || !do_out ||
-        !dXh || !drel_slab || !loss_slab)
-        return IDDGCN_E_BAD_ARG;
+    if (const int rc = check_distmult_heads(dim_ok(d), n_nodes, R, n_blocks, seg_ptr, perm, Xh, Xt, r_idx, rel, do_out,
+                                            dXh, drel_slab, loss_slab))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
-#define HK(DD, RT) hipLaunchKernelGGL((distmult_heads_kernel<DD, RT>), dim3(n_blocks), dim3(256), 0, st, n_nodes, R, seg_ptr, perm, Xh, Xt, r_idx, rel, y, scale, p_out, s_out, ds_out, do_out, dXh, drel_slab, loss_slab)
-#define HKR(DD)                                            \
-    {                                                      \
-        if (R <= 1) HK(DD, 1);                             \
-        else if (R <= 2) HK(DD, 2);                        \
-        else if (R <= 4) HK(DD, 4);                        \
-        else HK(DD, 8);                                    \
-    }
-    switch (d) {
-        case 32: HKR(32); break;
-        case 64: HKR(64); break;
-        case 128: HKR(128); break;
-        default: HKR(256); break;
-    }
-#undef HKR
-#undef HK
+    for_width(d, [&](auto D) {
+        for_rel_bucket(R, [&](auto RT) {
+            hipLaunchKernelGGL((distmult_heads_kernel<decltype(D)::value, decltype(RT)::value>), dim3(n_blocks), dim3(256),
+                               0, st, n_nodes, R, seg_ptr, perm, Xh, Xt, r_idx, rel, y, scale, p_out, s_out, ds_out,
+                               do_out, dXh, drel_slab, loss_slab);
+        });
+    });
     return launch_status();
 }
 
@@ -5597,14 +5639,10 @@ int iddgcn_seg_gather_reduce_f32(void* stream, int n_nodes, int d, const int* se
     if (n_nodes == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = grid_for(n_nodes, d / 4);
-#define GK(DD) hipLaunchKernelGGL(seg_gather_reduce_kernel<DD>, dim3(grid), dim3(256), 0, st, n_nodes, seg_ptr, perm, coef, r_idx, rel, rows, X, out)
-    switch (d) {
-        case 32: GK(32); break;
-        case 64: GK(64); break;
-        case 128: GK(128); break;
-        default: GK(256); break;
-    }
-#undef GK
+    for_width(d, [&](auto D) {
+        hipLaunchKernelGGL(seg_gather_reduce_kernel<decltype(D)::value>, dim3(grid), dim3(256), 0, st, n_nodes, seg_ptr,
+                           perm, coef, r_idx, rel, rows, X, out);
+    });
     return launch_status();
 }
 
@@ -5617,26 +5655,12 @@ int iddgcn_tail_seg_reduce_f32(void* stream, int n_nodes, int d, int R, const in
     if (n_nodes == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = grid_for(n_nodes, 64);       // one wave per node
-#define TK(DD, RR) hipLaunchKernelGGL((tail_seg_reduce_kernel<DD, RR>), dim3(grid), dim3(256), 0, st, n_nodes, seg_ptr, h_idx, W, dO, P, p_rel_stride, dP, dp_rel_stride, dsum, dWedge)
-#define TKR(DD)                \
-    switch (R) {               \
-        case 1: TK(DD, 1); break; \
-        case 2: TK(DD, 2); break; \
-        case 3: TK(DD, 3); break; \
-        case 4: TK(DD, 4); break; \
-        case 5: TK(DD, 5); break; \
-        case 6: TK(DD, 6); break; \
-        case 7: TK(DD, 7); break; \
-        default: TK(DD, 8); break; \
-    }
-    switch (d) {
-        case 32: TKR(32); break;
-        case 64: TKR(64); break;
-        case 128: TKR(128); break;
-        default: TKR(256); break;
-    }
-#undef TKR
-#undef TK
+    for_width(d, [&](auto D) {
+        for_rel<1>(R, [&](auto Rc) {
+            hipLaunchKernelGGL((tail_seg_reduce_kernel<decltype(D)::value, decltype(Rc)::value>), dim3(grid), dim3(256), 0,
+                               st, n_nodes, seg_ptr, h_idx, W, dO, P, p_rel_stride, dP, dp_rel_stride, dsum, dWedge);
+        });
+    });
     return launch_status();
 }
 
@@ -5651,14 +5675,10 @@ int iddgcn_head_bwd_node_f32(void* stream, int n_nodes, int d, int R, const floa
     if (n_nodes == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = grid_for(n_nodes, d / 4);
-#define HK(DD) hipLaunchKernelGGL(head_bwd_node_kernel<DD>, dim3(grid), dim3(256), 0, st, n_nodes, R, dO, P, p_rel_stride, Ssm, W, hseg_ptr, hperm, dWedge, ep_in, dP, dp_rel_stride, dsum, dz)
-    switch (d) {
-        case 32: HK(32); break;
-        case 64: HK(64); break;
-        case 128: HK(128); break;
-        default: HK(256); break;
-    }
-#undef HK
+    for_width(d, [&](auto D) {
+        hipLaunchKernelGGL(head_bwd_node_kernel<decltype(D)::value>, dim3(grid), dim3(256), 0, st, n_nodes, R, dO, P,
+                           p_rel_stride, Ssm, W, hseg_ptr, hperm, dWedge, ep_in, dP, dp_rel_stride, dsum, dz);
+    });
     return launch_status();
 }
 
@@ -5729,19 +5749,7 @@ int iddgcn_rowgemm_bf16(void* stream, const iddgcn_rowgemm_t* a) {
     if (a->planes) return IDDGCN_E_BAD_ARG;
     RowGemmP p = to_p(*a);
     p.accumulate = 0;
-    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-    if (a->R == 8 && a->v_idx && !a->coef_idx && !a->a_idx && !a->b_trans && !dsig && al16(a->A) && al16(a->C) &&
-        al16(a->coef) && al16(a->V) && (a->v_rel_stride & 3) == 0) {
-        launch_fwd_gather8((hipStream_t)stream, p);
-        return launch_status();
-    }
-    V3Sel sel;
-    sel.nv = a->R == 0 ? 0 : a->R == 1 ? 1 : a->R == 2 ? 2 : a->R <= 4 ? 4 : 8;
-    sel.aux = dsig;
-    sel.hc = a->R > 0;
-    RowGemmBatch pb;
-    pb.p[0] = p;
-    launch_v3((hipStream_t)stream, pb, 1, sel, true);
+    launch_rowgemm((hipStream_t)stream, p, 256, plan_rowgemm(p, 256, true));
     return launch_status();
 }
 
@@ -5750,71 +5758,38 @@ int iddgcn_gemm_tn_bf16(void* stream, long long M, int d, const void* A, const v
     if (d != 256) return IDDGCN_E_BAD_DIM;
     if (M < 0 || n_blocks < 1 || !A || !B || !slab || !C) return IDDGCN_E_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    long long rpb = (M + n_blocks - 1) / n_blocks;
-    rpb = ((rpb + 31) / 32) * 32;
-    if (rpb < 32) rpb = 32;
-    hipLaunchKernelGGL(gemm_tn256_bf16t_kernel, dim3(n_blocks), dim3(512), 0, st, M, rpb,
+    hipLaunchKernelGGL(gemm_tn256_bf16t_kernel, dim3(n_blocks), dim3(512), 0, st, M, tn_rows_per_block(M, n_blocks),
                        (const __bf16*)A, (const __bf16*)B, slab);
-    int rc = launch_status();
-    if (rc) return rc;
-    const long long n = (long long)d * d;
-    launch_reduce_slabs(st, n_blocks, n, slab, C, accumulate, 1.0f);
-    return launch_status();
+    return reduce_tn_slabs(st, n_blocks, d, slab, C, accumulate);
 }
 
 int iddgcn_sigma_tn_ranges(long long M) {
-    const long long nt = (M + stn::TR - 1) / stn::TR;
-    long long nr = nt < 128 ? nt : 128;
-    if (nr < 1) nr = 1;
-    const long long tpb = (nt + nr - 1) / nr > 0 ? (nt + nr - 1) / nr : 1;
-    nr = (nt + tpb - 1) / tpb;
-    return (int)((nr + 7) / 8 * 8 > 0 ? (nr + 7) / 8 * 8 : 8);
+    const long long nr = (split_tiles(M, stn::TR, 128).blocks + 7) / 8 * 8;
+    return (int)(nr > 0 ? nr : 8);
 }
 
 int iddgcn_sigma_tn_bf16(void* stream, long long M, int d, const void* dO, void* X, const float* S, float* slab,
                          long long slab_floats, float* dS, int precision) {
-    if (d != 256) return IDDGCN_E_BAD_DIM;
-    // the weights as a bf16 hi + lo pair for the fp32-operand modes, rounded to bf16 for IDDGCN_GEMM_BF16; nothing else
-    if (precision != IDDGCN_GEMM_EXACT_F32 && precision != IDDGCN_GEMM_SPLIT_F16 && precision != IDDGCN_GEMM_BF16X3 &&
-        precision != IDDGCN_GEMM_BF16)
-        return IDDGCN_E_BAD_ARG;
-    if (M < 0 || !S || !slab || !dS || (M > 0 && (!dO || !X))) return IDDGCN_E_BAD_ARG;
-    if (((uintptr_t)dO & 15) || ((uintptr_t)X & 15)) return IDDGCN_E_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    const long long nt = (M + stn::TR - 1) / stn::TR;
-    const int nr = iddgcn_sigma_tn_ranges(M);
-    const long long tpb = nt > 0 ? (nt + nr - 1) / nr : 1;
-    const long long n = (long long)d * d;
-    if (slab_floats < nr * n) return IDDGCN_E_BAD_ARG;
-    if (precision == IDDGCN_GEMM_BF16)
-        hipLaunchKernelGGL(sigma_tn_bf16_kernel<true>, dim3((unsigned)(2 * nr)), dim3(512), 0, st, M, (int)tpb, nr,
-                           (const __bf16*)dO, (__bf16*)X, S, slab);
-    else
-        hipLaunchKernelGGL(sigma_tn_bf16_kernel<false>, dim3((unsigned)(2 * nr)), dim3(512), 0, st, M, (int)tpb, nr,
-                           (const __bf16*)dO, (__bf16*)X, S, slab);
-    int rc = launch_status();
-    if (rc) return rc;
-    launch_reduce_slabs(st, nr, n, slab, dS, 0, 1.0f);
-    return launch_status();
+    // the weights as a bf16 hi + lo pair for the fp32-operand modes, rounded to bf16 for IDDGCN_GEMM_BF16; nothing else
+    return sigma_tn(st, M, d, tn_precision_ok(precision) || precision == IDDGCN_GEMM_BF16, dO, X, S, slab, slab_floats,
+                    dS, stn::TR, [&](dim3 grid, int tpb, int nr) {
+                        if (precision == IDDGCN_GEMM_BF16)
+                            hipLaunchKernelGGL(sigma_tn_bf16_kernel<true>, grid, dim3(512), 0, st, M, tpb, nr,
+                                               (const __bf16*)dO, (__bf16*)X, S, slab);
+                        else
+                            hipLaunchKernelGGL(sigma_tn_bf16_kernel<false>, grid, dim3(512), 0, st, M, tpb, nr,
+                                               (const __bf16*)dO, (__bf16*)X, S, slab);
+                    });
 }
 
 int iddgcn_sigma_tn_f32(void* stream, long long M, int d, const float* dO, float* X, const float* S, float* slab,
                         long long slab_floats, float* dS, int precision) {
-    if (d != 256) return IDDGCN_E_BAD_DIM;
-    if (precision != IDDGCN_GEMM_BF16X3) return IDDGCN_E_BAD_ARG;
-    if (M < 0 || !S || !slab || !dS || (M > 0 && (!dO || !X))) return IDDGCN_E_BAD_ARG;
-    if (((uintptr_t)dO & 15) || ((uintptr_t)X & 15)) return IDDGCN_E_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    const long long nt = (M + st3::TR - 1) / st3::TR;
-    const int nr = iddgcn_sigma_tn_ranges(M);
-    const long long tpb = nt > 0 ? (nt + nr - 1) / nr : 1;
-    const long long n = (long long)d * d;
-    if (slab_floats < nr * n) return IDDGCN_E_BAD_ARG;
-    hipLaunchKernelGGL(sigma_tn_b3_kernel, dim3((unsigned)(2 * nr)), dim3(768), 0, st, M, (int)tpb, nr, dO, X, S, slab);
-    int rc = launch_status();
-    if (rc) return rc;
-    launch_reduce_slabs(st, nr, n, slab, dS, 0, 1.0f);
-    return launch_status();
+    return sigma_tn(st, M, d, precision == IDDGCN_GEMM_BF16X3, dO, X, S, slab, slab_floats, dS, st3::TR,
+                    [&](dim3 grid, int tpb, int nr) {
+                        hipLaunchKernelGGL(sigma_tn_b3_kernel, grid, dim3(768), 0, st, M, tpb, nr, dO, X, S, slab);
+                    });
 }
 
 int iddgcn_combine_bf16(void* stream, int M, int d, int R, const float* Y, const int* idx, const float* coef,
@@ -5831,10 +5806,9 @@ int iddgcn_distmult_bce_bf16(void* stream, long long T, int d, int R, const floa
                              const void* Xt, const int* t_idx, const int* r_idx, const float* rel, const float* y,
                              float scale, float* p_out, float* s_out, float* ds_out, void* do_out,
                              float* drel_slab, float* loss_slab, int n_blocks) {
-    if (d != 256) return IDDGCN_E_BAD_DIM;
-    if (R < 1 || R > MAX_R) return IDDGCN_E_BAD_REL;
-    if (T < 0 || n_blocks < 1 || !Xh || !h_idx || !Xt || !r_idx || !rel) return IDDGCN_E_BAD_ARG;
-    if (y && (!ds_out || !do_out || !drel_slab || !loss_slab)) return IDDGCN_E_BAD_ARG;
+    if (const int rc = check_distmult(d == 256, T, R, n_blocks, Xh, h_idx, Xt, r_idx, rel, y, ds_out, do_out,
+                                      drel_slab, loss_slab))
+        return rc;
     if (T == 0) return 0;
     hipLaunchKernelGGL((distmult_kernel<256, true>), dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, T, R, Xh, h_idx,
                        (const float*)Xt, t_idx, r_idx, rel, y, scale, p_out, s_out, ds_out, (float*)do_out, drel_slab,
@@ -5846,18 +5820,15 @@ int iddgcn_distmult_bce_heads_bf16(void* stream, int n_nodes, int d, int R, cons
                                    const float* Xh, const void* Xt, const int* r_idx, const float* rel,
                                    const float* y, float scale, float* p_out, float* s_out, float* ds_out,
                                    void* do_out, float* dXh, float* drel_slab, float* loss_slab, int n_blocks) {
-    if (d != 256) return IDDGCN_E_BAD_DIM;
-    if (R < 1 || R > MAX_R) return IDDGCN_E_BAD_REL;
-    if (n_nodes < 0 || n_blocks < 1 || !seg_ptr || !perm || !Xh || !Xt || !r_idx || !rel || !do_out || !dXh ||
-        !drel_slab || !loss_slab)
-        return IDDGCN_E_BAD_ARG;
+    if (const int rc = check_distmult_heads(d == 256, n_nodes, R, n_blocks, seg_ptr, perm, Xh, Xt, r_idx, rel, do_out,
+                                            dXh, drel_slab, loss_slab))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
-#define HKB(RT) hipLaunchKernelGGL((distmult_heads_kernel<256, RT, true>), dim3(n_blocks), dim3(256), 0, st, n_nodes, R, seg_ptr, perm, Xh, (const float*)Xt, r_idx, rel, y, scale, p_out, s_out, ds_out, (float*)do_out, dXh, drel_slab, loss_slab)
-    if (R <= 1) HKB(1);
-    else if (R <= 2) HKB(2);
-    else if (R <= 4) HKB(4);
-    else HKB(8);
-#undef HKB
+    for_rel_bucket(R, [&](auto RT) {
+        hipLaunchKernelGGL((distmult_heads_kernel<256, decltype(RT)::value, true>), dim3(n_blocks), dim3(256), 0, st,
+                           n_nodes, R, seg_ptr, perm, Xh, (const float*)Xt, r_idx, rel, y, scale, p_out, s_out, ds_out,
+                           (float*)do_out, dXh, drel_slab, loss_slab);
+    });
     return launch_status();
 }
 
@@ -5926,18 +5897,10 @@ int iddgcn_tail_seg_reduce_bf16(void* stream, int n_nodes, int d, int R, const i
                           nullptr, nullptr);
         return launch_status();
     }
-#define TKB(RR) hipLaunchKernelGGL((tail_seg_reduce_kernel<256, RR, true>), dim3(grid), dim3(256), 0, st, n_nodes, seg_ptr, h_idx, W, d_o, P, p_rel_stride, dP, dp_rel_stride, dsum, dWedge)
-    switch (R) {
-        case 1: TKB(1); break;
-        case 2: TKB(2); break;
-        case 3: TKB(3); break;
-        case 4: TKB(4); break;
-        case 5: TKB(5); break;
-        case 6: TKB(6); break;
-        case 7: TKB(7); break;
-        default: TKB(8); break;
-    }
-#undef TKB
+    for_rel<1>(R, [&](auto Rc) {
+        hipLaunchKernelGGL((tail_seg_reduce_kernel<256, decltype(Rc)::value, true>), dim3(grid), dim3(256), 0, st, n_nodes,
+                           seg_ptr, h_idx, W, d_o, P, p_rel_stride, dP, dp_rel_stride, dsum, dWedge);
+    });
     return launch_status();
 }
 

@@ -32,8 +32,8 @@ Three input families:
      e = MFMA_ADD, T the sum of moduli of the element's terms.
 
 Error model, each term from the source:
-  * bf16 hi + lo weights (iddgcn_hip.hip:637-647, 1775-1783, 4881-4892: hi = bf16(w), lo = bf16(w - hi)): w - hi is
-    within half a bf16 ulp of w, 2^-8 2^e with 2^e <= |w|; its own ulp is then at most 2^(e-16), so
+  * bf16 hi + lo weights (iddgcn_hip.hip: rowgemm256_v3_kernel with BF, sigma_tn_bf16_kernel and
+    fwd_gather8_bf16_kernel: hi = bf16(w), lo = bf16(w - hi)): w - hi is within half a bf16 ulp of w, 2^-8 2^e with 2^e <= |w|; its own ulp is then at most 2^(e-16), so
     |w - hi - lo| <= 2^-17 |w| = REP_HL.  (2^-18 |w| is not a bound: test_selfcheck_hilo_representation finds random
     weights beyond it.)  A bf16 x bf16 product is exact in fp32; n = 2 D (two MFMAs per k-step), one product a hi + a lo
     is one add: HL_SINGLE = REP_HL + MFMA_ADD (1 + 2^-8).
@@ -129,7 +129,7 @@ def _gen(*seed):
 
 
 def hilo(w):
-    """The kernels' weight pieces (iddgcn_hip.hip:637-647): hi = bf16(w), lo = bf16(w - hi), as fp64."""
+    """The kernels' weight pieces (iddgcn_hip.hip, rowgemm256_v3_kernel with BF): hi = bf16(w), lo = bf16(w - hi), as fp64."""
     hi = w.float().to(BF16).float()
     lo = (w.float() - hi).to(BF16).float()
     return hi.double(), lo.double()
@@ -1098,11 +1098,13 @@ def test_selfcheck_tail_seg_mfma8_bounds():
 # The VALU bf16 forms: iddgcn_tail_seg_reduce_bf16 (R < 8, or h_idx), iddgcn_combine_bf16, iddgcn_distmult_bce(_heads)_bf16
 # =============================================================================================================
 @gpu
-@pytest.mark.parametrize("case", K.GRAPHS)
-@pytest.mark.parametrize("R,h_idx", [(1, False), (2, False), (4, True), (7, False), (8, True)])
+@pytest.mark.parametrize("R,h_idx,case",
+                         [(R, h, case) for case in K.GRAPHS
+                          for R, h in [(1, False), (2, False), (4, True), (7, False), (8, True)]] +
+                         [(3, True, "tiny"), (5, False, "tiny"), (6, True, "tiny")])
 def test_tail_seg_reduce_bf16_valu_vs_fp64(R, h_idx, case, cuda):
-    """tail_seg_reduce_kernel<256, R, BF>: the step-kernel module's bound builder fed the widened bf16 rows; with and
-    without dsum, twice."""
+    """tail_seg_reduce_kernel<256, R, BF>, every R = 1 .. 8: the step-kernel module's bound builder fed the widened
+    bf16 rows; with and without dsum, twice."""
     N, T, t, ptr, h, W, dO, P = K.tail_inputs(case, R, D, 13 * R + len(case))
     dO = dO.to(BF16)
     if not h_idx:
@@ -1116,7 +1118,7 @@ def test_tail_seg_reduce_bf16_valu_vs_fp64(R, h_idx, case, cuda):
 
 
 @gpu
-@pytest.mark.parametrize("R", [0, 1, 2, 8])
+@pytest.mark.parametrize("R", [0, 1, 2, 3, 4, 5, 6, 7, 8])
 def test_combine_bf16_per_element(R, cuda):
     """iddgcn_combine_bf16 (the run form writing bf16): the fp64 sigmoid with the combine bound of test_gpu_mfma_gemms
     carried through it, then the bf16 interval."""
@@ -1205,11 +1207,11 @@ DM_BF_RAW = ("p", "s", "ds", "do", "drel_slab", "loss_slab")
 
 
 @gpu
-@pytest.mark.parametrize("T", [1, 255, 257, 3001])
-@pytest.mark.parametrize("R", [2, 8])
+@pytest.mark.parametrize("R,T", [(R, T) for T in (1, 255, 257, 3001) for R in (2, 8)] + [(1, 257), (4, 257)])
 def test_distmult_bf16_training_vs_fp64(R, T, cuda):
     """iddgcn_distmult_bce_bf16 and _heads_bf16, training seed: s, p, ds, drel, the loss and dXh per element at the
-    step-kernel module's bounds, the bf16 do inside its interval, do_out aliasing Xt and not; twice."""
+    step-kernel module's bounds, the bf16 do inside its interval, do_out aliasing Xt and not; twice.  R = 1, 2, 4, 8
+    are the four relation-slot instantiations of distmult_heads_kernel<256, RT, BF>."""
     c = dm_bf_case(R, T)
     refs = K.dm_ref(c, True)
     what = f"distmult_bf16 R{R} T{T}"
@@ -1364,7 +1366,7 @@ def test_step_with_row_gemm_exact4_at_d256(features, cuda):
 # =============================================================================================================
 # Part 2: split-fp16 operands (IDDGCN_GEMM_SPLIT_F16) and the planes tables, D = 256
 # =============================================================================================================
-REP16 = 2.0 ** -22            # hi + lo of a scaled value while lo is a normal fp16 (iddgcn_hip.hip:448-477)
+REP16 = 2.0 ** -22            # hi + lo of a scaled value while lo is a normal fp16 (iddgcn_hip.hip: split16, split16_same)
 ABS_SAME = 2.0 ** -39         # split16_same with lo subnormal: 2^-25 of the scaled value, whose row / block max >= 2^14
 ABS_W = 2.0 ** -50            # split16 (lo carried at 2^11): 2^-36 of the scaled value, column max >= 2^14
 SLACK = 1 + 2.0 ** -9         # second-order terms of the products of the errors above
@@ -1892,10 +1894,11 @@ def test_planes_consumers_dense_per_element(cuda):
 
 
 @gpu
-@pytest.mark.parametrize("R", [0, 1, 2])
+@pytest.mark.parametrize("R", [0, 1, 2, 3, 4, 5, 6, 7, 8])
 def test_planes_producers_per_element(R, cuda):
-    """The planes-out combine and the gathered forward writing C as planes: the decoded output within the fp64
-    sigmoid's bar of test_gpu_mfma_gemms plus the encoding's 2^-24 (the encoding itself is test_gpu_planes.py's)."""
+    """The planes-out combine (every R) and the gathered forward writing C as planes (it exists for R = 1, 2): the
+    decoded output within the fp64 sigmoid's bar of test_gpu_mfma_gemms plus the encoding's 2^-24 (the encoding itself
+    is test_gpu_planes.py's)."""
     for M in (1, 63, 65, 785):
         c = G.comb_case(256, M, R, "run")
         whole, out = guarded(cuda, M, 256)
@@ -1905,7 +1908,7 @@ def test_planes_producers_per_element(R, cuda):
         guard_intact(whole, what)
         ref, bound = G.comb_ref(c)
         assert_within(split_planes_decode(out.cpu()), ref, bound + 2.0 ** -24, what)
-    if R:
+    if R in (1, 2):
         for M in (1, 33, 785):
             c = G.row_case(256, M, f"gather_R{R}_sig" if R != 2 else "gather_R2_sig", "dense", "runs13")
             c.A = split_planes_decode(split_planes_encode(unit_rows(_gen(M, 109), M))).float()

@@ -174,7 +174,7 @@ def test_gemm_tn(D, cuda):
     assert torch.equal(C1, C2)              # slab reduction in block order: deterministic
 
 
-@pytest.mark.parametrize("D", [32, 256])
+@pytest.mark.parametrize("D", DIMS)
 def test_gemm_tn_narrow(D, cuda):
     g = torch.Generator().manual_seed(19 + D)
     M, R = 9001, 3
@@ -202,23 +202,30 @@ def test_alpha(D, cuda):
     assert torch.equal(S2, S[idx]) and torch.equal(W2, W[idx])
 
 
-@pytest.mark.parametrize("D", DIMS)
-def test_combine(D, cuda):
+# every combine_kernel<D, R> instantiation: R = 2 at M = 3001 per width (ids "32" .. "256"), the other relation counts
+# at M = 257
+COMBINE_ARMS = [(D, 2, 3001) for D in DIMS] + [(D, R, 257) for D in DIMS for R in range(9) if R != 2]
+
+
+@pytest.mark.parametrize("D,R,M", COMBINE_ARMS, ids=[str(D) if R == 2 else f"{D}-R{R}" for D, R, M in COMBINE_ARMS])
+def test_combine(D, R, M, cuda):
     g = torch.Generator().manual_seed(29 + D)
-    N, M, R = 200, 3001, 2
-    Y, P = rnd(N, D, dev=cuda, gen=g), rnd(R, N, D, dev=cuda, gen=g)
+    N = 200
+    Y, P = rnd(N, D, dev=cuda, gen=g), rnd(max(R, 1), N, D, dev=cuda, gen=g)[:R]
     W = torch.rand(N, R, generator=g, dtype=torch.float64).to(cuda)
     h = torch.randint(0, N, (M,), generator=g).to(cuda)
     t = torch.randint(0, N, (M,), generator=g).to(cuda)
     out = torch.empty(M, D, device=cuda)
-    ops.combine(Y.float(), W.float(), P.float(), out, y_idx=t.int(), coef_idx=h.int(), v_idx=t.int())
+    ops.combine(Y.float(), W.float(), P.float(), out, y_idx=t.int(), coef_idx=h.int(), v_idx=t.int(), v_rel_stride=N * D)
     ref = Y[t] + sum(W[h, r:r + 1] * P[r][t] for r in range(R))
     close(out, torch.sigmoid(ref), 1e-5)
 
 
-@pytest.mark.parametrize("R", [0, 1, 2, 3, 4])
-@pytest.mark.parametrize("M,order", [(1, "sorted"), (63, "sorted"), (65, "unsorted"), (20_011, "sorted"),
-                                     (20_011, "unsorted"), (20_011, "one_run")])
+# R = 5 .. 8 (the other arms of run_combine256_kernel<R> and combine_kernel<256, R>) at one small unsorted M
+@pytest.mark.parametrize("M,order,R", [(M, order, R) for R in (0, 1, 2, 3, 4)
+                                       for M, order in [(1, "sorted"), (63, "sorted"), (65, "unsorted"), (20_011, "sorted"),
+                                                        (20_011, "unsorted"), (20_011, "one_run")]] +
+                         [(65, "unsorted", R) for R in (5, 6, 7, 8)])
 def test_combine_runs(R, M, order, cuda):
     """Run-combine path (D = 256, y_idx is v_idx, per-edge coef): equal to torch and bitwise to the
     generic edge-parallel kernel (reached by passing a copy of the index as v_idx)."""

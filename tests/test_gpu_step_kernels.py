@@ -767,14 +767,19 @@ def _tail_check(cuda, case, R, D, split_w=False):
     _same(a, c, ("dP", "dsum"), what + " vs per-edge W")
 
 
+# every graph at D = 64, 256 x R = 1, 2, 4, 8; the other of the 32 tail_seg_reduce_kernel<D, R> instantiations on the
+# smallest graph (R = 2 at D = 32, 128: test_tail_seg_reduce_h_idx_slot_partials)
+TAIL_ARMS = [(R, D, case) for case in GRAPHS for D in (64, 256) for R in (1, 2, 4, 8)] + \
+            [(R, D, "tiny") for D in (32, 64, 128, 256) for R in range(1, 9)
+             if not (D in (64, 256) and R in (1, 2, 4, 8)) and not (D in (32, 128) and R == 2)]
+
+
 @gpu
-@pytest.mark.parametrize("case", GRAPHS)
-@pytest.mark.parametrize("D", [64, 256])
-@pytest.mark.parametrize("R", [1, 2, 4, 8])
+@pytest.mark.parametrize("R,D,case", TAIL_ARMS)
 def test_tail_seg_reduce_h_idx_vs_fp64(R, D, case, cuda):
     """tail_seg_reduce with h_idx (the config-3 / config-4 form; <256, 2> is the headline's instantiation): dP, dsum
     and dWedge per element against fp64, with and without dsum, on row-range views of larger P / dP tables, twice,
-    and bitwise the per-edge-W form fed by gather_rows."""
+    and bitwise the per-edge-W form fed by gather_rows.  Every (D, R) instantiation of the kernel is launched."""
     _tail_check(cuda, case, R, D)
 
 

@@ -40,6 +40,21 @@ def test_library_is_tied_to_its_sources(tmp_path):
     files = _srchash.source_files()
     assert "iddgcn_amd/csrc/iddgcn_hip.hip" in files and "include/iddgcn.h" in files
     assert "iddgcn_amd/csrc/device_flags.txt" in files
+    # every file a source reaches through a quoted #include (transitively) is a build input of the digest too
+    included, todo = set(), [f for f in files if f.startswith("iddgcn_amd/csrc/")]
+    while todo:
+        src = todo.pop()
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(ROOT, src)).read(), flags=re.M):
+            # the compiler's search: beside the including file, then -I include
+            rels = [os.path.relpath(os.path.normpath(os.path.join(ROOT, d, inc)), ROOT)
+                    for d in (os.path.dirname(src), "include")]
+            rel = next((r for r in rels if os.path.exists(os.path.join(ROOT, r))), None)
+            assert rel, (src, inc)
+            if rel.startswith(("iddgcn_amd/", "include/")) and rel not in included:
+                included.add(rel)
+                todo.append(rel)
+    assert not included - set(files), sorted(included - set(files))
+    assert "include/iddgcn.h" in included
     # a stand-in library at the right ABI but built from other sources
     src = tmp_path / "stale.c"
     src.write_text(f'int iddgcn_abi_version(void) {{ return {_lib.ABI_VERSION}; }}\n'
