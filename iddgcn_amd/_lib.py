@@ -67,6 +67,17 @@ class MaskExplainArgs(ctypes.Structure):
     ]
 
 
+class ExplainCurvesArgs(ctypes.Structure):
+    """Mirror of iddgcn_explain_curves_t (include/iddgcn_explain.h)."""
+    _fields_ = [
+        ("N", ci), ("d", ci), ("R", ci), ("k", ci), ("Q", ci),
+        ("h", vp), ("r", vp), ("t", vp), ("qptr", vp),
+        ("crel", vp), ("ccol", vp), ("crole", vp), ("cstep", vp), ("cval", vp),
+        ("E", vp), ("K", vp * 3), ("S", vp * 3), ("Wa", vp * 3), ("ba", vp * 3), ("rel", vp),
+        ("del_", vp), ("ins", vp),           # `del` is a Python keyword
+    ]
+
+
 TN_BATCH = 4
 SCREEN_TAIL, SCREEN_HEAD = 0, 1                   # include/iddgcn_screen.h IDDGCN_SCREEN_*
 TOPK_MAX = 64
@@ -144,6 +155,8 @@ SIGNATURES = {
     "iddgcn_explain_topk_f32": (ci, [vp, ci, ci, vp, vp, vp, vp, vp, vp]),
     # batched mask explainers (added symbol only)
     "iddgcn_mask_explain_f32": (ci, [vp, ctypes.POINTER(MaskExplainArgs)]),
+    # deletion / insertion curves of explanations (added symbol only)
+    "iddgcn_explain_curves_f32": (ci, [vp, ctypes.POINTER(ExplainCurvesArgs)]),
     # include/iddgcn_ground_truth.h (explanation ground truth; added symbols only)
     "iddgcn_gt_sim_lists_workspace": (ci, [cll, ctypes.POINTER(cll)]),
     "iddgcn_gt_sim_lists": (ci, [vp, cll, ci, vp, vp, vp, vp, vp, vp, cll]),

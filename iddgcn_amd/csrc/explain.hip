@@ -17,6 +17,8 @@
 // sort of 64-bit (value, entry id) keys in LDS merged into the running top 64.
 //
 // mask_explain_kernel (further down): every epoch of one triple's mask training in one workgroup.
+//
+// curves_kernel (last): the deletion and insertion curves of an explanation, a tile of edited forwards per workgroup.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -765,6 +767,184 @@ __global__ __launch_bounds__(NT) void mask_explain_kernel(const iddgcn_mask_expl
     }
 }
 
+// ---- deletion / insertion curves -------------------------------------------------------------------------------
+// curves_kernel: one workgroup per (query, tile of CV_VT variants); a variant is one edited copy of the query's two
+// adjacency rows, so a tile is CV_ROWS = 2 CV_VT row vectors (2 u: the head row of variant u, 2 u + 1: its tail row).
+// The candidates' E rows are staged once (the first ES_ROWS; the others come from global memory) and every variant's
+// AE rows are built from them; then the mask explainer's forward runs on all rows of the tile at once: a thread loads
+// its column of K^l_r (or S^l) 32 elements at a time and applies it to every row before the next load, so a weight
+// element read serves CV_ROWS fmaf.  AE, P and the activations live in LDS; group grp of D lanes owns relations grp,
+// grp + GR in the AE and P passes and rows grp RW .. in the combine.  The sums are matvec2's: four fmaf chains per
+// element, (c0 + c1) + (c2 + c3); a row's arithmetic does not depend on its place in the tile.
+//   LDS at D = 64: es 80 KB + AE 32 KB + P 32 KB + x 8 KB + 0.5 KB = 152.5 KB of the CU's 160 KB (one workgroup per CU).
+constexpr int CV_VT = 8;
+constexpr int CV_ROWS = 2 * CV_VT;
+constexpr int CV_ES_BYTES = 80 * 1024;     // E rows kept in LDS: 320 candidates at d = 64, 640 at d = 32
+
+// column k of rows · M for NR row vectors (LDS, stride `rs` floats, 16-byte aligned): Mk = M + k, M (D, D) row-major
+template <int D, int NR>
+__device__ __forceinline__ void matvec_rows(const float* __restrict__ Mk, const float* rows, int rs, float* y) {
+    float c4[NR][4];
+#pragma unroll
+    for (int j = 0; j < NR; ++j) c4[j][0] = c4[j][1] = c4[j][2] = c4[j][3] = 0.f;
+#pragma unroll
+    for (int i0 = 0; i0 < D; i0 += 32) {
+        float kv[32];
+#pragma unroll
+        for (int u = 0; u < 32; ++u) kv[u] = Mk[(size_t)(i0 + u) * D];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < 32; u += 4)
+#pragma unroll
+            for (int j = 0; j < NR; ++j) {
+                const f32x4 av = *(const f32x4*)(rows + j * rs + i0 + u);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) c4[j][(u >> 3) & 3] = fmaf(av[c], kv[u + c], c4[j][(u >> 3) & 3]);
+            }
+    }
+#pragma unroll
+    for (int j = 0; j < NR; ++j) y[j] = (c4[j][0] + c4[j][1]) + (c4[j][2] + c4[j][3]);
+}
+
+template <int D>
+__global__ __launch_bounds__(NT) void curves_kernel(const iddgcn_explain_curves_t a, int n_tiles) {
+    constexpr int GR = NT / D;                 // groups of D lanes: 4 / 8
+    constexpr int RPG = MAX_R / GR;            // relations per group: 2 / 1
+    constexpr int RW = CV_ROWS / GR;           // rows per group in the combine: 4 / 2
+    constexpr int ES_ROWS = CV_ES_BYTES / (4 * D);
+    __shared__ float es[ES_ROWS * D];
+    __shared__ __attribute__((aligned(16))) float AE[MAX_R][CV_ROWS][D];
+    __shared__ float P[MAX_R][CV_ROWS][D];
+    __shared__ __attribute__((aligned(16))) float x[2][CV_ROWS][D];
+    __shared__ float zs[CV_VT][MAX_R];
+    __shared__ float w[CV_VT][MAX_R];
+    __shared__ int rstart[MAX_R + 1];
+
+    const int tid = threadIdx.x;
+    const int R = a.R;
+    const int q = blockIdx.x / n_tiles;
+    const int v0 = (blockIdx.x % n_tiles) * CV_VT;
+    const int nv = 2 * (a.k + 1);              // variants 0 .. k: deletion points, k + 1 .. 2 k + 1: insertion points
+    const int hh = a.h[q], rr = a.r[q], tt = a.t[q];
+    const long long c0 = a.qptr[q];
+    const int n = (int)(a.qptr[q + 1] - c0);
+    const int* crel = a.crel + c0;
+    const int* ccol = a.ccol + c0;
+    const int* crole = a.crole + c0;
+    const int* cstep = a.cstep + c0;
+    const float* cval = a.cval + c0;
+    const int k = tid % D, grp = tid / D;
+
+    // variants past the last repeat it (computed, never stored)
+    int pt[CV_VT];
+    bool isins[CV_VT];
+#pragma unroll
+    for (int u = 0; u < CV_VT; ++u) {
+        const int vi = v0 + u < nv ? v0 + u : nv - 1;
+        isins[u] = vi > a.k;
+        pt[u] = isins[u] ? vi - (a.k + 1) : vi;
+    }
+
+    // the relation segments of the candidate list, x^0 = E[h] / E[t] in every variant, the staged E rows
+    if (tid <= MAX_R) rstart[tid] = n;
+    __syncthreads();
+    for (int j = tid; j < n; j += NT) {
+        const int r1 = crel[j];
+        const int r0 = j ? crel[j - 1] : -1;
+        for (int r = r0 + 1; r <= r1; ++r) rstart[r] = j;
+    }
+    for (int idx = tid; idx < CV_ROWS * D; idx += NT) {
+        const int row = idx / D;
+        x[0][row][idx % D] = a.E[(size_t)((row & 1) ? tt : hh) * D + idx % D];
+    }
+    {
+        const int ns = n < ES_ROWS ? n : ES_ROWS;
+        for (int idx = tid; idx < ns * D; idx += NT) es[idx] = a.E[(size_t)ccol[idx / D] * D + idx % D];
+    }
+    __syncthreads();
+
+    // AE rows of every variant: candidates ascending, one chain per (row, relation, column); a candidate the variant
+    // drops (or that does not feed the side) enters with a zero multiplier: fmaf(0, e, acc) is acc
+#pragma unroll
+    for (int ri = 0; ri < RPG; ++ri) {
+        const int r = grp + ri * GR;
+        if (r < R) {
+            float acc[CV_ROWS];
+#pragma unroll
+            for (int j = 0; j < CV_ROWS; ++j) acc[j] = 0.f;
+            const int j1 = rstart[r + 1];
+            for (int j = rstart[r]; j < j1; ++j) {
+                const float val = cval[j];
+                const int st = cstep[j], role = crole[j];
+                const float ev = j < ES_ROWS ? es[j * D + k] : a.E[(size_t)ccol[j] * D + k];
+                const float vh = (role & 1) ? val : 0.f, vt = (role & 2) ? val : 0.f;
+#pragma unroll
+                for (int u = 0; u < CV_VT; ++u) {
+                    const bool flipped = st >= 0 && st < pt[u];
+                    const bool keep = flipped == isins[u];
+                    acc[2 * u] = fmaf(keep ? vh : 0.f, ev, acc[2 * u]);
+                    acc[2 * u + 1] = fmaf(keep ? vt : 0.f, ev, acc[2 * u + 1]);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < CV_ROWS; ++j) AE[r][j][k] = acc[j];
+        }
+    }
+    __syncthreads();
+
+    // forward: the reference layer on the CV_ROWS rows
+    for (int l = 0; l < 3; ++l) {
+        const int cur = l & 1;
+        for (int item = grp; item < CV_VT * R; item += GR) {
+            const int u = item / R, r = item % R;
+            const float z = group_sum<D>(x[cur][2 * u][k] * a.Wa[l][(size_t)k * R + r]);
+            if (k == 0) zs[u][r] = z + a.ba[l][r];
+        }
+#pragma unroll
+        for (int ri = 0; ri < RPG; ++ri) {
+            const int r = grp + ri * GR;
+            if (r < R) {
+                float y[CV_ROWS];
+                matvec_rows<D, CV_ROWS>(a.K[l] + (size_t)r * D * D + k, &AE[r][0][0], D, y);
+#pragma unroll
+                for (int j = 0; j < CV_ROWS; ++j) P[r][j][k] = y[j];
+            }
+        }
+        __syncthreads();
+        if (tid < CV_VT * R) {
+            const int u = tid / R, r = tid % R;
+            float mx = -INFINITY;
+            for (int i = 0; i < R; ++i) mx = fmaxf(mx, zs[u][i]);
+            float sum = 0.f;
+            for (int i = 0; i < R; ++i) sum += expf(zs[u][i] - mx);
+            w[u][r] = sigmoid_ref(expf(zs[u][r] - mx) / sum);
+        }
+        __syncthreads();
+        {
+            float y[RW];
+            matvec_rows<D, RW>(a.S[l] + k, &x[cur][grp * RW][0], D, y);
+#pragma unroll
+            for (int j = 0; j < RW; ++j) {
+                const int row = grp * RW + j;
+                float v = y[j];
+                for (int r = 0; r < R; ++r) v = fmaf(w[row >> 1][r], P[r][row][k], v);
+                x[1 - cur][row][k] = sigmoid_ref(v);
+            }
+        }
+        __syncthreads();
+    }
+
+    // DistMult of every variant (x^3 sits in x[1])
+    for (int u = grp; u < CV_VT; u += GR) {
+        const float s = group_sum<D>(x[1][2 * u][k] * a.rel[(size_t)rr * D + k] * x[1][2 * u + 1][k]);
+        const int vi = v0 + u;
+        if (k == 0 && vi < nv) {
+            float* out = vi > a.k ? a.ins + (size_t)q * (a.k + 1) + (vi - (a.k + 1)) : a.del + (size_t)q * (a.k + 1) + vi;
+            *out = sigmoid_ref(s);
+        }
+    }
+}
+
 }  // namespace xpl
 
 extern "C" {
@@ -861,6 +1041,30 @@ int iddgcn_mask_explain_f32(void* stream, const iddgcn_mask_explain_t* args) {
         hipLaunchKernelGGL(mask_explain_kernel<64>, dim3((unsigned)a.n_queries), dim3(NT), 0, st, a);
     else
         hipLaunchKernelGGL(mask_explain_kernel<32>, dim3((unsigned)a.n_queries), dim3(NT), 0, st, a);
+    return (int)hipGetLastError();
+}
+
+int iddgcn_explain_curves_f32(void* stream, const iddgcn_explain_curves_t* args) {
+    using namespace xpl;
+    if (!args) return IDDGCN_E_BAD_ARG;
+    const iddgcn_explain_curves_t& a = *args;
+    if (a.d != 32 && a.d != 64) return IDDGCN_E_BAD_DIM;
+    if (a.R < 1 || a.R > MAX_R) return IDDGCN_E_BAD_REL;
+    if (a.k < 1 || a.k > IDDGCN_TOPK_MAX || a.Q < 0 || a.N < 1) return IDDGCN_E_BAD_ARG;
+    if (a.Q == 0) return 0;
+    if (!a.h || !a.r || !a.t || !a.qptr || !a.E || !a.rel || !a.del || !a.ins) return IDDGCN_E_BAD_ARG;
+    // the candidate arrays may be null when every segment is empty: they are then never read
+    for (int l = 0; l < 3; ++l)
+        if (!a.K[l] || !a.S[l] || !a.Wa[l] || !a.ba[l]) return IDDGCN_E_BAD_ARG;
+    if ((uintptr_t)a.E & 15) return IDDGCN_E_BAD_ARG;
+    const int n_tiles = (2 * (a.k + 1) + CV_VT - 1) / CV_VT;
+    if ((long long)a.Q * n_tiles > 0x7fffffffLL) return IDDGCN_E_BAD_ARG;
+    const dim3 grid((unsigned)(a.Q * n_tiles));
+    hipStream_t st = (hipStream_t)stream;
+    if (a.d == 64)
+        hipLaunchKernelGGL(curves_kernel<64>, grid, dim3(NT), 0, st, a, n_tiles);
+    else
+        hipLaunchKernelGGL(curves_kernel<32>, grid, dim3(NT), 0, st, a, n_tiles);
     return (int)hipGetLastError();
 }
 

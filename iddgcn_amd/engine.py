@@ -1283,6 +1283,64 @@ class Engine:
                                       out["entry"], out["grad"], eoc)
         return out
 
+    def edit_curves(self, params, adj, triples, cand, K, max_entries=1 << 22):
+        """Deletion and insertion curves of Q triples in one fused launch per chunk (ops.explain_curves).
+
+        A variant of (h, r, t) edits only the adjacency rows h and t, and the prediction reads A_r only through
+        AE_r[h] and AE_r[t]: 2 (K + 1) variants are 2 (K + 1) pairs of edited rows pushed through the three layers,
+        with no node table built.  ``cand``: explain.curve_steps' dict over ``adj`` (host arrays ``qptr``, ``rel``,
+        ``col``, ``role``, ``step``, ``val``).  The queries run in chunks of at most ``max_entries`` candidates, at
+        least one query each.  fp32 features with D in {32, 64}, 1 <= R <= 8, unsharded engine: IddgcnError otherwise
+        (explain.fidelity_curves(fused=False) covers the rest).  Returns (deletion, insertion): (Q, K + 1) fp32
+        device tensors."""
+        self._require_unsharded("edit_curves")
+        N, R, D, dev = self.N, self.R, self.D, self.device
+        if D not in (32, 64) or self.features != "f32" or not 1 <= R <= 8:
+            raise L.IddgcnError("edit_curves takes D in {32, 64}, fp32 features and 1 <= R <= 8: use "
+                                "explain.fidelity_curves(fused=False) for this engine")
+        K = int(K)
+        if not 1 <= K <= L.TOPK_MAX:
+            raise L.IddgcnError(f"edit_curves: K must be in [1, {L.TOPK_MAX}], got {K}")
+        if adj.num_entities != N or adj.num_relations != R:
+            raise L.IddgcnError("edit_curves: the adjacency is not this engine's size")
+        if int(max_entries) < 1:
+            raise ValueError(f"max_entries must be positive, got {max_entries}")
+        q = self._triples(triples, "triples", "triple")
+        Q = q.shape[0]
+        qp = np.asarray(cand["qptr"], np.int64)
+        C = len(cand["rel"])
+        if qp.shape != (Q + 1,) or qp[0] != 0 or qp[-1] != C or (np.diff(qp) < 0).any():
+            raise L.IddgcnError("edit_curves: cand['qptr'] must be (Q + 1,), ascending from 0 to the candidate count")
+        if any(len(cand[nm]) != C for nm in ("col", "role", "step", "val")):
+            raise L.IddgcnError("edit_curves: the candidate arrays must be of one length")
+        if C:
+            rel, col, role, step = (np.asarray(cand[nm]) for nm in ("rel", "col", "role", "step"))
+            inner = np.ones(C, bool)
+            inner[qp[:-1][qp[:-1] < C]] = False                    # a segment's first candidate has no predecessor
+            if (rel.min() < 0 or rel.max() >= R or col.min() < 0 or col.max() >= N or role.min() < 1 or
+                    role.max() > 3 or step.min() < -1 or step.max() >= K or (np.diff(rel)[inner[1:]] < 0).any()):
+                raise L.IddgcnError("edit_curves: candidate out of range (rel, col, role in 1..3, step in [-1, K)) "
+                                    "or relations not ascending inside a query")
+        g = lambda x, dt: torch.as_tensor(np.ascontiguousarray(x, dtype=dt), device=dev)  # noqa: E731
+        dele = torch.empty(Q, K + 1, dtype=torch.float32, device=dev)
+        ins = torch.empty(Q, K + 1, dtype=torch.float32, device=dev)
+        if Q == 0:
+            return dele, ins
+        h, r, t, qptr = g(q[:, 0], np.int32), g(q[:, 1], np.int32), g(q[:, 2], np.int32), g(qp, np.int64)
+        crel, ccol, crole, cstep = (g(cand[nm], np.int32) for nm in ("rel", "col", "role", "step"))
+        cval = g(cand["val"], np.float32)
+        Kw, S, Wa, ba = (tuple(params[f"{nm}{l}"] for l in (1, 2, 3)) for nm in ("K", "S", "Wa", "ba"))
+        self.finish_pending()
+        q0 = 0
+        while q0 < Q:
+            q1 = min(Q, max(q0 + 1, int(np.searchsorted(qp, qp[q0] + int(max_entries), side="right")) - 1))
+            with self._mark("edit_curves"):
+                # the chunk's own qptr slice: its offsets stay absolute, into the full candidate arrays
+                ops.explain_curves(params["E"], Kw, S, Wa, ba, params["rel"], h[q0:q1], r[q0:q1], t[q0:q1],
+                                   qptr[q0:q1 + 1], crel, ccol, crole, cstep, cval, K, dele[q0:q1], ins[q0:q1])
+            q0 = q1
+        return dele, ins
+
 
 def step_flops(N, R, D, T, M):
     """Algorithmic work of one training step (W_gemm)."""

@@ -26,6 +26,9 @@ use a specific one (default: numpy N(0,1) with the given seed).
 ``mask_explainer_batched`` (``gnn_explainer_batched`` / ``iddgcn_explainer_batched``) runs the same mask training from
 each triple's candidate entries alone, every epoch of a triple in one workgroup, with the shared Adam kept as sparse
 per-entry state (see the section below).
+
+``fidelity_curves`` scores any of their outputs against the model itself: the deletion and insertion curves of each
+triple's explanation, every variant of a triple in one fused kernel (``fidelity_summary``, ``random_explanations``).
 """
 import time
 
@@ -594,6 +597,192 @@ def iddgcn_explainer_batched(model, adjacency_data, test_triples, num_epochs=10,
         raise IddgcnError("target_ratios needs one entry per relation")
     return mask_explainer_batched(model, adjacency_data, test_triples, num_epochs=num_epochs,
                                   learning_rate=learning_rate, threshold=threshold, target_ratios=target_ratios, **kw)
+
+
+# -- fidelity: deletion and insertion curves -------------------------------------------------------
+# Do the edges an explanation names drive the prediction?  deletion[q, j]: the probability of triple q with the first
+# j explanation edges removed from the adjacency; insertion[q, j]: with ONLY those edges left in rows h and t.  A
+# variant edits rows h and t alone, and the prediction reads A_r only through AE_r[h] and AE_r[t], so all 2 (K + 1)
+# variants of a triple are pairs of edited rows pushed through the three layers (Engine.edit_curves, one workgroup per
+# tile of variants); no ground-truth file is involved.
+def _padded_explanations(preds, n):
+    """(n, K, 3) int64 with -1 rows past a short list's end, from an (n, K, 3) array or a list of (k_i, 3) arrays."""
+    if isinstance(preds, np.ndarray) and preds.ndim == 3:
+        out = preds.astype(np.int64)
+    else:
+        lists = [np.asarray(p, np.int64).reshape(-1, 3) for p in preds]
+        out = np.full((len(lists), max((len(p) for p in lists), default=1), 3), -1, np.int64)
+        for j, p in enumerate(lists):
+            out[j, :len(p)] = p
+    if out.shape[0] != n or out.shape[2] != 3:
+        raise IddgcnError(f"preds must hold one (k, 3) explanation per triple ({n}), got {out.shape}")
+    if not 1 <= out.shape[1] <= TOPK_MAX:
+        raise IddgcnError(f"explanations must have between 1 and {TOPK_MAX} edges, got {out.shape[1]}")
+    return out
+
+
+def _row_candidates(dadj, triples):
+    """mask_candidates restricted to role != 0 (the entry's row is h or t) and each candidate's stored value."""
+    qptr, entry, crel, ccol, crole = mask_candidates(dadj, triples)
+    keep = crole != 0
+    q_of = np.repeat(np.arange(len(qptr) - 1), np.diff(qptr))[keep]
+    qptr = np.concatenate([[0], np.cumsum(np.bincount(q_of, minlength=len(qptr) - 1))]).astype(np.int64)
+    entry = entry[keep]
+    val = dadj.base_values.cpu().numpy().astype(np.float32)[entry]
+    return qptr, q_of, entry, crel[keep], ccol[keep], crole[keep], val
+
+
+def curve_steps(dadj, triples, preds, undirected=False):
+    """The candidates of each triple's deletion / insertion curves and the step at which each one flips (host).
+
+    A triple's candidates are the stored, non-placeholder entries of ``dadj`` whose row is h or t (mask_candidates
+    with role != 0, same order).  Explanation edge j = (i, rel, c) names the stored entry (row i, col c) of ``rel``;
+    the candidate it names gets ``step`` j unless an earlier edge named it.  An edge that names no candidate of its
+    triple (not stored, only its column is h or t, a duplicate, padding) is inert.  ``undirected``: edge j also flips
+    the entry (c, rel, i) when that is a candidate.  Returns a dict of host arrays: ``qptr`` (n + 1,) int64; per
+    candidate ``entry``, ``rel``, ``col``, ``role``, ``step`` (int32; -1: never flips) and ``val`` (fp32);
+    ``effective`` (n, K) bool: edge j flipped at least one candidate; ``K``."""
+    tr = _as_triples(triples)
+    n, N, total = len(tr), dadj.num_entities, dadj.total_nnz
+    ex = _padded_explanations(preds, n)
+    K = ex.shape[1]
+    qptr, q_of, entry, crel, ccol, crole, val = _row_candidates(dadj, tr)
+    # stored (rel, row, col) -> entry id, through one sorted 64-bit key
+    row, col, rel, real = _entry_table(dadj)
+    ids = np.flatnonzero(real)
+    key = (rel[ids] * N + row[ids]) * N + col[ids]
+    order = np.argsort(key, kind="stable")
+    key, ids = key[order], ids[order]
+    # (triple, entry id) -> candidate index: the candidate lists ascend by (triple, entry)
+    ckey = q_of.astype(np.int64) * total + entry
+    step = np.full(len(entry), K, np.int64)
+    e_i, e_r, e_c = ex[:, :, 0], ex[:, :, 1], ex[:, :, 2]
+    ok = (e_i >= 0) & (e_i < N) & (e_c >= 0) & (e_c < N) & (e_r >= 0) & (e_r < dadj.num_relations)
+    qq, jj = np.nonzero(ok)
+    for a, b in ((e_i, e_c), (e_c, e_i)) if undirected else ((e_i, e_c),):
+        want = (e_r[qq, jj] * N + a[qq, jj]) * N + b[qq, jj]
+        at = np.minimum(np.searchsorted(key, want), max(len(key) - 1, 0))
+        stored = key[at] == want if len(key) else np.zeros(len(want), bool)
+        wantc = qq[stored] * total + ids[at[stored]]
+        atc = np.minimum(np.searchsorted(ckey, wantc), max(len(ckey) - 1, 0))
+        hit = ckey[atc] == wantc if len(ckey) else np.zeros(len(wantc), bool)
+        np.minimum.at(step, atc[hit], jj[stored][hit])
+    step[step == K] = -1
+    effective = np.zeros((n, K), bool)
+    effective[q_of[step >= 0], step[step >= 0]] = True
+    i32 = np.int32
+    return dict(qptr=qptr, entry=entry.astype(i32), rel=crel.astype(i32), col=ccol.astype(i32),
+                role=crole.astype(i32), step=step.astype(i32), val=val, effective=effective, K=K)
+
+
+def _curves_layered(eng, params, dadj, triples, cand, K):
+    """One set_values + Engine.predict per variant (any width and mode): the route a user had before the fused kernel,
+    its cross-check and its timing baseline."""
+    dev = eng.device
+    base = dadj.base_values.to(torch.float32)
+    n = len(triples)
+    out = torch.empty(2, n, K + 1, dtype=torch.float32, device=dev)
+    qp = cand["qptr"]
+    entry = torch.as_tensor(cand["entry"].astype(np.int64), device=dev)
+    step = torch.as_tensor(cand["step"].astype(np.int64), device=dev)
+    val = torch.as_tensor(cand["val"], device=dev)
+    for q in range(n):
+        ed = eng.edges(triples[q][None])
+        e, st, v = (x[qp[q]:qp[q + 1]] for x in (entry, step, val))
+        zero = torch.zeros_like(v)
+        for j in range(K + 1):
+            flipped = (st >= 0) & (st < j)
+            for which, keep in ((0, ~flipped), (1, flipped)):
+                vals = base.clone()
+                vals[e] = torch.where(keep, v, zero)
+                dadj.set_values(vals)
+                out[which, q, j] = eng.predict(params, dadj, ed)[0]
+    dadj.set_values(base)
+    return out[0], out[1]
+
+
+def fidelity_curves(model, adjacency_data, test_triples, preds, *, undirected=False, fused=None, stats=None):
+    """Deletion and insertion curves of one ranked explanation per test triple.
+
+    ``preds``: an (n, K, 3) array or a list of (k_i, 3) arrays of (head, rel, tail) edges, best first, as the
+    explainers return them (K = the longest list, 1 <= K <= 64; a short list is padded with inert steps).
+    deletion[q, j] is the model's probability for triple q with the candidates named by its first j edges set to 0,
+    insertion[q, j] the probability with only those kept and every other stored entry of rows h and t set to 0
+    (curve_steps has the exact rules); deletion[:, 0] is the unedited prediction.
+
+    ``fused``: None picks the fused kernel (Engine.edit_curves) for fp32 features, D in {32, 64}, R <= 8 and an
+    unsharded engine; False runs one set_values + predict per variant on the layered kernels (any width); True
+    demands the kernel (IddgcnError outside its envelope).  ``stats``: an optional dict that receives ``fused``,
+    ``candidates`` and, on the fused route, ``launch_events`` (a pair of recorded device events around the launches).
+    Returns a dict of numpy arrays: ``p`` (n,), ``deletion`` (n, K + 1), ``insertion`` (n, K + 1), ``effective``
+    (n, K) bool."""
+    eng, params = _model_state(model)
+    N, R = model.num_entities, model.num_relations
+    triples = _as_triples(test_triples)
+    if len(triples) and (triples[:, 1].min() < 0 or triples[:, 1].max() >= R):
+        raise IddgcnError("triple relation index out of range [0, num_relations)")
+    can_fuse = (eng.D in (32, 64) and eng.features == "f32" and 1 <= R <= 8 and eng.node_shard is None and
+                eng.spmm_shard is None and eng.row_shard is None)
+    if fused is None:
+        fused = can_fuse
+    elif fused and not can_fuse:
+        raise IddgcnError("fidelity_curves: the fused kernel takes D in {32, 64}, fp32 features, 1 <= R <= 8 and an "
+                          "unsharded engine: use fused=False for this model")
+    dadj = DeviceAdjacency(get_adj_mats(adjacency_data, N, R), N, eng.device)
+    cand = curve_steps(dadj, triples, preds, undirected)
+    K = cand["K"]
+    if fused:
+        ev = None
+        if stats is not None:
+            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            ev[0].record()
+        dele, ins = eng.edit_curves(params, dadj, triples, cand, K)
+        if ev is not None:
+            ev[1].record()
+            stats.update(launch_events=ev)
+    else:
+        dele, ins = _curves_layered(eng, params, dadj, triples, cand, K)
+    if stats is not None:
+        stats.update(fused=bool(fused), candidates=int(len(cand["entry"])))
+    dele, ins = dele.cpu().numpy(), ins.cpu().numpy()
+    return dict(p=dele[:, 0].copy(), deletion=dele, insertion=ins, effective=cand["effective"])
+
+
+def fidelity_summary(curves):
+    """Per-triple and mean fidelity of fidelity_curves' result (host).  fidelity_plus = p - deletion[:, K]: the drop
+    when the whole explanation is deleted (larger: the edges matter); fidelity_minus = p - insertion[:, K]: what is
+    lost when only the explanation is kept (smaller: the edges suffice); deletion_auc / insertion_auc: the trapezoid
+    area under each curve over j / K; effective_share: the share of explanation edges that flipped a candidate.
+    Returns a dict: the four per-triple (n,) float64 arrays, ``effective_share`` and ``mean`` (a dict of their
+    means)."""
+    p = np.asarray(curves["p"], np.float64)
+    dele, ins = np.asarray(curves["deletion"], np.float64), np.asarray(curves["insertion"], np.float64)
+    K = dele.shape[1] - 1
+    if K < 1 or ins.shape != dele.shape or p.shape != dele.shape[:1]:
+        raise ValueError(f"curves must hold p (n,) and deletion / insertion (n, K + 1), got {p.shape}, {dele.shape}, "
+                         f"{ins.shape}")
+    auc = lambda y: (y[:, :-1] + y[:, 1:]).sum(1) / (2.0 * K)  # noqa: E731
+    eff = np.asarray(curves["effective"], bool)
+    out = dict(fidelity_plus=p - dele[:, K], fidelity_minus=p - ins[:, K], deletion_auc=auc(dele),
+               insertion_auc=auc(ins), effective_share=float(eff.mean()) if eff.size else 0.0)
+    out["mean"] = {k: float(v.mean()) if len(v) else 0.0 for k, v in out.items() if isinstance(v, np.ndarray)}
+    return out
+
+
+def random_explanations(dadj, triples, k, seed=0):
+    """The baseline beside every fidelity number: per triple, k stored entries drawn without replacement from its
+    candidate rows (the entries whose row is h or t), uniformly, as (head, rel, tail) edges.  Returns a list of
+    (min(k, candidates), 3) int64 arrays; seeded (numpy default_rng)."""
+    tr = _as_triples(triples)
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"k must be positive, got {k}")
+    qptr, q_of, entry, crel, ccol, _, _ = _row_candidates(dadj, tr)
+    row = np.concatenate(dadj.rows)
+    draw = np.random.default_rng(seed).random(len(entry))
+    order = np.lexsort((draw, q_of))                                # a random order inside every triple's segment
+    edges = np.stack([row[entry], crel.astype(np.int64), ccol.astype(np.int64)], 1)[order]
+    return [edges[qptr[q]:min(qptr[q] + k, qptr[q + 1])] for q in range(len(tr))]
 
 
 def explanation_metrics(preds, gt, top=5, exp_num=10):

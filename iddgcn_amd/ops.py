@@ -1011,6 +1011,67 @@ def mask_explain(E, K, S, Wa, ba, rel, h, r, t, qptr, entry, crel, ccol, crole, 
     return out
 
 
+def explain_curves(E, K, S, Wa, ba, rel, h, r, t, qptr, crel, ccol, crole, cstep, cval, k, deletion=None,
+                   insertion=None):
+    """Deletion and insertion curves of Q explanations (iddgcn_explain_curves_f32), one launch: per query 2 (k + 1)
+    edited forwards.  E (N, D); K, S, Wa, ba: the three layers' (R, D, D), (D, D), (D, R), (R,); rel (R, D); h, r, t
+    (Q,) int32; qptr (Q + 1,) int64 into the candidate arrays crel / ccol / crole / cstep (int32) and cval (fp32):
+    explain.curve_steps' lists (a slice of qptr keeps its absolute offsets).  Returns (deletion, insertion), (Q, k + 1)
+    fp32 each, allocated when not given.  D in {32, 64}, 1 <= R <= 8, 1 <= k <= TOPK_MAX.  Index values are the
+    caller's to validate (IDDGCN_CHECK_INDICES=1 checks them here)."""
+    N, D = E.shape
+    R = rel.shape[0]
+    Q = h.shape[0]
+    k = int(k)
+    if not 1 <= k <= L.TOPK_MAX:
+        raise L.IddgcnError(f"explain_curves: k must be in [1, {L.TOPK_MAX}]")
+    _req(E, _F32, (N, D), "E")
+    _req(rel, _F32, (R, D), "rel")
+    if not (len(K) == len(S) == len(Wa) == len(ba) == 3):
+        raise L.IddgcnError("explain_curves: K, S, Wa, ba must hold the three layers")
+    for l in range(3):
+        if K[l] is None or S[l] is None or Wa[l] is None or ba[l] is None:
+            raise L.IddgcnError("explain_curves: every layer's K, S, Wa, ba is required")
+        _req(K[l], _F32, (R, D, D), f"K{l + 1}")
+        _req(S[l], _F32, (D, D), f"S{l + 1}")
+        _req(Wa[l], _F32, (D, R), f"Wa{l + 1}")
+        _req(ba[l], _F32, (R,), f"ba{l + 1}")
+    _idx_ok(h, Q, N, "h")
+    _idx_ok(r, Q, R, "r")
+    _idx_ok(t, Q, N, "t")
+    _req(qptr, torch.int64, (Q + 1,), "qptr")
+    C = crel.shape[0]
+    _idx_ok(crel, C, R, "crel")
+    _idx_ok(ccol, C, N, "ccol")
+    _idx_ok(crole, C, 4, "crole")
+    _req(cstep, _I32, (C,), "cstep")
+    _req(cval, _F32, (C,), "cval")
+    dev = E.device
+    deletion = torch.empty(Q, k + 1, dtype=_F32, device=dev) if deletion is None else deletion
+    insertion = torch.empty(Q, k + 1, dtype=_F32, device=dev) if insertion is None else insertion
+    _req(deletion, _F32, (Q, k + 1), "deletion")
+    _req(insertion, _F32, (Q, k + 1), "insertion")
+    if E.data_ptr() & 15:
+        raise L.IddgcnError("explain_curves: E must be 16-byte aligned")
+    if CHECK_INDEX_RANGES and Q:
+        qp = qptr.cpu()
+        if int(qp[0]) < 0 or bool((qp[1:] < qp[:-1]).any()) or int(qp[-1]) > C:
+            raise L.IddgcnError("explain_curves: qptr must ascend within [0, len(crel)]")
+        if C and (int(cstep.min()) < -1 or int(cstep.max()) >= k):
+            raise L.IddgcnError("explain_curves: cstep must lie in [-1, k)")
+    a = L.ExplainCurvesArgs()
+    a.N, a.d, a.R, a.k, a.Q = N, D, R, k, Q
+    a.h, a.r, a.t, a.qptr = h.data_ptr(), r.data_ptr(), t.data_ptr(), qptr.data_ptr()
+    a.crel, a.ccol, a.crole, a.cstep, a.cval = crel.data_ptr(), ccol.data_ptr(), crole.data_ptr(), \
+        cstep.data_ptr(), cval.data_ptr()
+    a.E, a.rel = E.data_ptr(), rel.data_ptr()
+    for l in range(3):
+        a.K[l], a.S[l], a.Wa[l], a.ba[l] = K[l].data_ptr(), S[l].data_ptr(), Wa[l].data_ptr(), ba[l].data_ptr()
+    a.del_, a.ins = deletion.data_ptr(), insertion.data_ptr()
+    L.check(L.lib().iddgcn_explain_curves_f32(_stream(), ctypes.byref(a)), "explain_curves")
+    return deletion, insertion
+
+
 # -- explanation ground truth (include/iddgcn_ground_truth.h) ------------------------------------
 def _triples3(t, name):
     _req(t, _I64, None, name)

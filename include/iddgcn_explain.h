@@ -124,6 +124,45 @@ typedef struct {
  * num_epochs >= 0; a null pointer (target_ratios excepted) or a misaligned E: IDDGCN_E_BAD_ARG. */
 int iddgcn_mask_explain_f32(void* stream, const iddgcn_mask_explain_t* args);
 
+/*
+ * Deletion and insertion curves of Q explanations (explain.fidelity_curves): 2 (k + 1) edited forwards per query
+ * against one pass over the weights per tile of variants.  A query's candidates j = 0 .. n-1 are the stored,
+ * non-placeholder entries of the full adjacency whose ROW is h or t (role_j != 0, bits as above), ascending entry id
+ * (so relation-major), each with its stored value val_j and a step_j: the position of the first explanation edge that
+ * names it, -1 when none does.  With F_i = {j : 0 <= step_j < i}, for i = 0 .. k:
+ *
+ *     del[q][i] = forward(keep_j = [j not in F_i]),   ins[q][i] = forward(keep_j = [j in F_i])
+ *     forward:  AE_r[h] = sum_{role_j & 1, rel_j = r} keep_j val_j E[col_j]  (one fmaf chain per column, j ascending;
+ *               a dropped candidate enters with the multiplier 0), AE_r[t] alike with role_j & 2;
+ *               then the mask explainer's forward above: softmax from the head row, w = sigmoid(softmax), DistMult.
+ *
+ * del[q][0] is the unedited prediction, ins[q][0] the prediction with both rows empty.  One workgroup per (query,
+ * tile of 8 variants); no atomics, no flags.  Every point has a fixed summation order that depends on the query's own
+ * candidates and on the SET F_i only: not on Q, k, the query's place in the batch, the other variants or the order of
+ * the steps inside F_i.
+ */
+typedef struct {
+    int N, d, R;
+    int k;                           /* explanation length: k + 1 points per curve, 1 <= k <= IDDGCN_TOPK_MAX */
+    int Q;
+    const int* h; const int* r; const int* t;                 /* per query, int32, validated by the caller */
+    const long long* qptr;           /* (Q + 1) candidate segments */
+    const int* crel; const int* ccol; const int* crole; const int* cstep;   /* per candidate; crel ascends in a segment */
+    const float* cval;               /* per candidate */
+    const float* E;                  /* (N, d), 16-byte aligned */
+    const float* K[3];               /* (R, d, d) */
+    const float* S[3];               /* (d, d) */
+    const float* Wa[3];              /* (d, R) */
+    const float* ba[3];              /* (R) */
+    const float* rel;                /* (R, d) */
+    float* del; float* ins;          /* (Q, k + 1) each */
+} iddgcn_explain_curves_t;
+
+/* d in {32, 64} (IDDGCN_E_BAD_DIM), 1 <= R <= 8 (IDDGCN_E_BAD_REL), 1 <= k <= IDDGCN_TOPK_MAX, Q >= 0 (0: nothing
+ * launched), N >= 1; a null pointer (the candidate arrays excepted: they are never read when every segment is empty)
+ * or a misaligned E: IDDGCN_E_BAD_ARG. */
+int iddgcn_explain_curves_f32(void* stream, const iddgcn_explain_curves_t* args);
+
 #ifdef __cplusplus
 }
 #endif
