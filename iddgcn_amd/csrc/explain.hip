@@ -26,18 +26,16 @@
 #include "iddgcn.h"
 #include "iddgcn_explain.h"
 #include "iddgcn_screen.h"
+#include "per_query.hpp"
 
 namespace xpl {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace pq;      // f32x4, sigmoid_fast, make_key, TK_BUF / TK_CH
 
 constexpr int MAX_R = 8;
 constexpr int NT = 256;            // 4 waves
 constexpr int QT = 8;              // queries per workgroup of seeds_kernel
 constexpr int NV = 2 * QT;         // row vectors: 2 qi = head of query qi, 2 qi + 1 = its tail
-
-// layer activations as the row GEMM's epilogue and screen_chain_kernel compute them
-__device__ __forceinline__ float sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 
 struct SeedP {
     int Q, N, R;
@@ -323,17 +321,7 @@ __global__ __launch_bounds__(NT) void row_grads_kernel(const RowP a) {
 }
 
 // ---- selection -------------------------------------------------------------------------------------------------
-constexpr int TK_BUF = 1024;                           // keys sorted per pass
-constexpr int TK_CH = TK_BUF - IDDGCN_TOPK_MAX;        // new candidates per pass; buf[TK_CH..) holds the running top
-
-// larger key = better candidate: value descending (-0.0 taken as +0.0), then id ascending; 0 = no candidate
-__device__ __forceinline__ unsigned long long make_key(float v, int c) {
-    if (v == 0.0f) v = 0.0f;
-    unsigned u = __float_as_uint(v);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)c);
-}
-
+// the value of a key of make_key (per_query.hpp)
 __device__ __forceinline__ float key_value(unsigned long long key) {
     const unsigned u = (unsigned)(key >> 32);
     return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
@@ -979,11 +967,9 @@ int iddgcn_explain_seeds_f32(void* stream, int Q, int N, int d, int R, const int
     a.Wa[0] = Wa2; a.Wa[1] = Wa3;
     a.rel = rel; a.G = G; a.p = p;
     const unsigned blocks = (unsigned)((Q + QT - 1) / QT);
-    hipStream_t st = (hipStream_t)stream;
-    if (d == 64)
-        hipLaunchKernelGGL(seeds_kernel<64>, dim3(blocks), dim3(NT), 0, st, a);
-    else
-        hipLaunchKernelGGL(seeds_kernel<32>, dim3(blocks), dim3(NT), 0, st, a);
+    for_small_width(d, [&](auto D) {
+        hipLaunchKernelGGL(seeds_kernel<decltype(D)::value>, dim3(blocks), dim3(NT), 0, (hipStream_t)stream, a);
+    });
     return (int)hipGetLastError();
 }
 
@@ -1001,11 +987,9 @@ int iddgcn_explain_row_grads_f32(void* stream, int Q, int N, int d, int R, const
     a.N = N; a.R = R;
     a.h = h; a.t = t; a.row_ptr = row_ptr; a.col = col; a.eoc = entry_of_csr;
     a.G = G; a.E = E; a.qptr = qptr; a.entry = entry; a.grad = grad;
-    hipStream_t st = (hipStream_t)stream;
-    if (d == 64)
-        hipLaunchKernelGGL(row_grads_kernel<64>, dim3((unsigned)Q), dim3(NT), 0, st, a);
-    else
-        hipLaunchKernelGGL(row_grads_kernel<32>, dim3((unsigned)Q), dim3(NT), 0, st, a);
+    for_small_width(d, [&](auto D) {
+        hipLaunchKernelGGL(row_grads_kernel<decltype(D)::value>, dim3((unsigned)Q), dim3(NT), 0, (hipStream_t)stream, a);
+    });
     return (int)hipGetLastError();
 }
 
@@ -1033,14 +1017,12 @@ int iddgcn_mask_explain_f32(void* stream, const iddgcn_mask_explain_t* args) {
         !a.alpha || !a.out)
         return IDDGCN_E_BAD_ARG;
     // the candidate arrays may be null when every segment is empty: they are then never read
-    for (int l = 0; l < 3; ++l)
-        if (!a.K[l] || !a.KT[l] || !a.S[l] || !a.ST[l] || !a.Wa[l] || !a.ba[l]) return IDDGCN_E_BAD_ARG;
+    if (!layers_ok(a.K, a.KT, a.S, a.ST, a.Wa, a.ba)) return IDDGCN_E_BAD_ARG;
     if ((uintptr_t)a.E & 15) return IDDGCN_E_BAD_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (a.d == 64)
-        hipLaunchKernelGGL(mask_explain_kernel<64>, dim3((unsigned)a.n_queries), dim3(NT), 0, st, a);
-    else
-        hipLaunchKernelGGL(mask_explain_kernel<32>, dim3((unsigned)a.n_queries), dim3(NT), 0, st, a);
+    for_small_width(a.d, [&](auto D) {
+        hipLaunchKernelGGL(mask_explain_kernel<decltype(D)::value>, dim3((unsigned)a.n_queries), dim3(NT), 0,
+                           (hipStream_t)stream, a);
+    });
     return (int)hipGetLastError();
 }
 
@@ -1054,17 +1036,14 @@ int iddgcn_explain_curves_f32(void* stream, const iddgcn_explain_curves_t* args)
     if (a.Q == 0) return 0;
     if (!a.h || !a.r || !a.t || !a.qptr || !a.E || !a.rel || !a.del || !a.ins) return IDDGCN_E_BAD_ARG;
     // the candidate arrays may be null when every segment is empty: they are then never read
-    for (int l = 0; l < 3; ++l)
-        if (!a.K[l] || !a.S[l] || !a.Wa[l] || !a.ba[l]) return IDDGCN_E_BAD_ARG;
+    if (!layers_ok(a.K, a.S, a.Wa, a.ba)) return IDDGCN_E_BAD_ARG;
     if ((uintptr_t)a.E & 15) return IDDGCN_E_BAD_ARG;
     const int n_tiles = (2 * (a.k + 1) + CV_VT - 1) / CV_VT;
     if ((long long)a.Q * n_tiles > 0x7fffffffLL) return IDDGCN_E_BAD_ARG;
     const dim3 grid((unsigned)(a.Q * n_tiles));
-    hipStream_t st = (hipStream_t)stream;
-    if (a.d == 64)
-        hipLaunchKernelGGL(curves_kernel<64>, grid, dim3(NT), 0, st, a, n_tiles);
-    else
-        hipLaunchKernelGGL(curves_kernel<32>, grid, dim3(NT), 0, st, a, n_tiles);
+    for_small_width(a.d, [&](auto D) {
+        hipLaunchKernelGGL(curves_kernel<decltype(D)::value>, grid, dim3(NT), 0, (hipStream_t)stream, a, n_tiles);
+    });
     return (int)hipGetLastError();
 }
 

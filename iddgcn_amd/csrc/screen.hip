@@ -16,19 +16,16 @@
 
 #include "iddgcn.h"
 #include "iddgcn_screen.h"
+#include "per_query.hpp"
 
 namespace scr {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace pq;      // f32x4, sigmoid_fast, ld4 / st4, make_key, TK_BUF / TK_CH
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int MAX_R = 8;
 constexpr int NT = 256;            // 4 waves
-
-// layer activations as the row GEMM's epilogue computes them (v_exp_f32 + v_rcp_f32, saturating to exactly 0 / 1)
-__device__ __forceinline__ float sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *(const f32x4*)p; }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *(f32x4*)p = v; }
 
 // wave w: column slab cs = w % CS (32 output columns), row group rg = w / CS (32 rows), as rowgemm_kernel
 template <int D>
@@ -200,17 +197,6 @@ __global__ __launch_bounds__(NT, 2) void screen_chain_kernel(const ScreenP p) {
 }
 
 // ---- selection -------------------------------------------------------------------------------------------------
-constexpr int TK_BUF = 1024;                           // keys sorted per pass
-constexpr int TK_CH = TK_BUF - IDDGCN_TOPK_MAX;        // new candidates per pass; buf[TK_CH..) holds the running top
-
-// larger key = better candidate: value descending (-0.0 taken as +0.0), then id ascending; 0 = no candidate
-__device__ __forceinline__ unsigned long long make_key(float v, int c) {
-    if (v == 0.0f) v = 0.0f;
-    unsigned u = __float_as_uint(v);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)c);
-}
-
 __device__ __forceinline__ bool in_sorted(const int* __restrict__ f, int n, int c) {
     int lo = 0, hi = n;
     while (lo < hi) {
@@ -338,7 +324,8 @@ int iddgcn_screen_chain_f32(void* stream, int Q, int N, int d, int R, int side, 
     // rows of ES1 and P are read as 16-byte vectors
     if (((uintptr_t)ES1 & 15) || ((uintptr_t)P & 15) || (p_layer_stride & 3) || (p_rel_stride & 3))
         return IDDGCN_E_BAD_ARG;
-    const int TR = d == 64 ? SC<64>::TR : SC<32>::TR;
+    int TR = 0;
+    for_small_width(d, [&](auto D) { TR = SC<decltype(D)::value>::TR; });
     ScreenP p;
     p.N = N; p.R = R; p.side = side;
     p.q_node = q_node; p.q_rel = q_rel;
@@ -356,11 +343,10 @@ int iddgcn_screen_chain_f32(void* stream, int Q, int N, int d, int R, int side, 
     p.groups = (p.ntiles + p.tpb - 1) / p.tpb;
     const long long blocks = (long long)Q * p.groups;
     if (blocks >= (1ll << 31)) return IDDGCN_E_BAD_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (d == 64)
-        hipLaunchKernelGGL(screen_chain_kernel<64>, dim3((unsigned)blocks), dim3(NT), 0, st, p);
-    else
-        hipLaunchKernelGGL(screen_chain_kernel<32>, dim3((unsigned)blocks), dim3(NT), 0, st, p);
+    for_small_width(d, [&](auto D) {
+        hipLaunchKernelGGL(screen_chain_kernel<decltype(D)::value>, dim3((unsigned)blocks), dim3(NT), 0,
+                           (hipStream_t)stream, p);
+    });
     return (int)hipGetLastError();
 }
 

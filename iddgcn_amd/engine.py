@@ -550,9 +550,54 @@ class Engine:
             return t
         return t[rows[0]:rows[1]] if dim == 0 else t[:, rows[0]:rows[1]]
 
+    @property
+    def sharded(self):
+        return self.node_shard is not None or self.spmm_shard is not None or self.row_shard is not None
+
     def _require_unsharded(self, what):
-        if self.node_shard is not None or self.spmm_shard is not None or self.row_shard is not None:
+        if self.sharded:
             raise L.IddgcnError(f"{what}: not available on an Engine with node_shard / spmm_shard / row_shard set")
+
+    def per_query_ok(self, any_small_shape=False):
+        """The envelope of the fused per-query kernels (csrc/screen.hip, csrc/explain.hip): D in {32, 64}, fp32
+        features, 1 <= R <= 8, an unsharded engine.  ``any_small_shape`` (rank_candidates, as it always was): every
+        D <= 64 and every R pass here."""
+        shape_ok = self.D <= 64 if any_small_shape else (self.D in (32, 64) and 1 <= self.R <= 8)
+        return shape_ok and self.features == "f32" and not self.sharded
+
+    def require_per_query(self, message):
+        if not self.per_query_ok():
+            raise L.IddgcnError(message)
+
+    def _predict_workspace(self):
+        """Any predict workspace (the per-query kernels read its node tables only), a one-edge one if none is cached."""
+        return next((w for (_, tr), w in self._ws.items() if not tr), None) or self.workspace(1, False)
+
+    def to_device(self, a, dtype=np.int32):
+        """A host array as a contiguous device tensor of ``dtype``."""
+        return torch.as_tensor(np.ascontiguousarray(a, dtype=dtype), device=self.device)
+
+    @staticmethod
+    def resolve_fused(fused, can_fuse, message, default=True):
+        """The ``fused`` argument of a method with a fused kernel and a layered path: None takes the kernel where it
+        applies (and ``default`` allows), True demands it (IddgcnError ``message`` outside its envelope), False the
+        layered path."""
+        if fused is None:
+            return bool(can_fuse and default)
+        if fused and not can_fuse:
+            raise L.IddgcnError(message)
+        return bool(fused)
+
+    @staticmethod
+    def _query_chunks(qp, max_entries):
+        """(q0, q1) query ranges that cover the host CSR pointer ``qp`` in order: at most ``max_entries`` candidates
+        each, at least one query."""
+        Q, q0, chunks = len(qp) - 1, 0, []
+        while q0 < Q:
+            q1 = min(Q, max(q0 + 1, int(np.searchsorted(qp, qp[q0] + int(max_entries), side="right")) - 1))
+            chunks.append((q0, q1))
+            q0 = q1
+        return chunks
 
     def _triples(self, triples, name, one):
         """(Q, 3) (h, r, t) as a checked int64 host array; the messages call the array ``name`` and a row ``one``."""
@@ -1094,16 +1139,15 @@ class Engine:
         if not 1 <= int(k) <= L.TOPK_MAX:
             raise ValueError(f"k must be in [1, {L.TOPK_MAX}], got {k}")
         self._require_unsharded("rank_candidates")
-        N, D, dev = self.N, self.D, self.device
+        N, dev = self.N, self.device
         k = int(k)
-        can_fuse = D <= 64 and self.features == "f32"
-        if fused is None:
-            fused = can_fuse and self.fused_screen_default
-        elif fused and not can_fuse:
-            raise L.IddgcnError("rank_candidates: the fused kernel takes D <= 64 with fp32 features")
+        # every D <= 64 and every R pass here: the C side (iddgcn_screen_chain_f32) refuses D outside {32, 64}, R > 8
+        fused = self.resolve_fused(fused, self.per_query_ok(any_small_shape=True),
+                                   "rank_candidates: the fused kernel takes D <= 64 with fp32 features",
+                                   self.fused_screen_default)
         q = self._triples(queries, "queries", "query")
         Q = q.shape[0]
-        i32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=dev)  # noqa: E731
+        i32 = self.to_device
         node = i32(q[:, 0] if side == "tail" else q[:, 2])
         target = i32(q[:, 2] if side == "tail" else q[:, 0])
         rel = i32(q[:, 1])
@@ -1131,7 +1175,7 @@ class Engine:
         if Q == 0:
             return out
         if fused:
-            ws = next((w for (_, tr), w in self._ws.items() if not tr), None) or self.workspace(1, False)
+            ws = self._predict_workspace()
         else:
             if min(chunk, Q) * N > np.iinfo(np.int32).max:
                 raise L.IddgcnError("too many scored edges for int32 indexing")
@@ -1233,17 +1277,14 @@ class Engine:
         in the caller's entry order, relation after relation, as the concatenation of ``value_grads``' list (rows of
         h relation by relation, then rows of t when t != h) — and ``grad`` (qptr[-1],), the gradient of
         ``scale * p_q`` w.r.t. that entry's value.  Every entry not listed has gradient exactly 0."""
-        self._require_unsharded("value_grads_batch")
+        self.require_per_query("value_grads_batch takes D in {32, 64}, fp32 features, 1 <= R <= 8 and an unsharded "
+                               "engine: use value_grads / explain.explaine (the per-triple path) for this engine")
         N, R, D, dev = self.N, self.R, self.D, self.device
-        if D not in (32, 64) or self.features != "f32":
-            raise L.IddgcnError("value_grads_batch takes D in {32, 64} with fp32 features: use value_grads / "
-                                "explain.explaine (the per-triple path) for this engine")
         q = self._triples(triples, "triples", "triple")
         Q = q.shape[0]
         if int(max_entries) < 1:
             raise ValueError(f"max_entries must be positive, got {max_entries}")
-        i32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=dev)  # noqa: E731
-        h, r, t = i32(q[:, 0]), i32(q[:, 1]), i32(q[:, 2])
+        h, r, t = (self.to_device(q[:, c]) for c in range(3))
         self.finish_pending()
         # candidate counts from the row degrees, prefix-summed on the device
         ptr = adj.fwd_ptr.view(R, N + 1)
@@ -1258,17 +1299,13 @@ class Engine:
                "grad": torch.empty(int(qp[-1]), dtype=torch.float32, device=dev)}
         if Q == 0:
             return out
-        ws = next((w for (_, tr), w in self._ws.items() if not tr), None) or self.workspace(1, False)
+        ws = self._predict_workspace()
         with self._mark("xb_node_tables"):
             self._node_tables(params, adj, ws)
         K = tuple(params[f"K{l}"] for l in (1, 2, 3))
         # an identity entry order (DeviceAdjacency.from_triples) needs no map
         eoc = None if adj.fwd_src is adj.fwd_pos else adj.fwd_src
-        chunks, q0 = [], 0
-        while q0 < Q:
-            q1 = max(q0 + 1, int(np.searchsorted(qp, qp[q0] + int(max_entries), side="right")) - 1)
-            chunks.append((q0, min(q1, Q)))
-            q0 = chunks[-1][1]
+        chunks = self._query_chunks(qp, max_entries)
         G = torch.empty(max(b - a for a, b in chunks), 2, R, D, dtype=torch.float32, device=dev)
         for q0, q1 in chunks:
             g = G[:q1 - q0]
@@ -1293,11 +1330,9 @@ class Engine:
         least one query each.  fp32 features with D in {32, 64}, 1 <= R <= 8, unsharded engine: IddgcnError otherwise
         (explain.fidelity_curves(fused=False) covers the rest).  Returns (deletion, insertion): (Q, K + 1) fp32
         device tensors."""
-        self._require_unsharded("edit_curves")
-        N, R, D, dev = self.N, self.R, self.D, self.device
-        if D not in (32, 64) or self.features != "f32" or not 1 <= R <= 8:
-            raise L.IddgcnError("edit_curves takes D in {32, 64}, fp32 features and 1 <= R <= 8: use "
-                                "explain.fidelity_curves(fused=False) for this engine")
+        self.require_per_query("edit_curves takes D in {32, 64}, fp32 features, 1 <= R <= 8 and an unsharded engine: "
+                               "use explain.fidelity_curves(fused=False) for this engine")
+        N, R, dev = self.N, self.R, self.device
         K = int(K)
         if not 1 <= K <= L.TOPK_MAX:
             raise L.IddgcnError(f"edit_curves: K must be in [1, {L.TOPK_MAX}], got {K}")
@@ -1321,24 +1356,21 @@ class Engine:
                     role.max() > 3 or step.min() < -1 or step.max() >= K or (np.diff(rel)[inner[1:]] < 0).any()):
                 raise L.IddgcnError("edit_curves: candidate out of range (rel, col, role in 1..3, step in [-1, K)) "
                                     "or relations not ascending inside a query")
-        g = lambda x, dt: torch.as_tensor(np.ascontiguousarray(x, dtype=dt), device=dev)  # noqa: E731
+        g = self.to_device
         dele = torch.empty(Q, K + 1, dtype=torch.float32, device=dev)
         ins = torch.empty(Q, K + 1, dtype=torch.float32, device=dev)
         if Q == 0:
             return dele, ins
-        h, r, t, qptr = g(q[:, 0], np.int32), g(q[:, 1], np.int32), g(q[:, 2], np.int32), g(qp, np.int64)
-        crel, ccol, crole, cstep = (g(cand[nm], np.int32) for nm in ("rel", "col", "role", "step"))
+        h, r, t, qptr = g(q[:, 0]), g(q[:, 1]), g(q[:, 2]), g(qp, np.int64)
+        crel, ccol, crole, cstep = (g(cand[nm]) for nm in ("rel", "col", "role", "step"))
         cval = g(cand["val"], np.float32)
         Kw, S, Wa, ba = (tuple(params[f"{nm}{l}"] for l in (1, 2, 3)) for nm in ("K", "S", "Wa", "ba"))
         self.finish_pending()
-        q0 = 0
-        while q0 < Q:
-            q1 = min(Q, max(q0 + 1, int(np.searchsorted(qp, qp[q0] + int(max_entries), side="right")) - 1))
+        for q0, q1 in self._query_chunks(qp, max_entries):
             with self._mark("edit_curves"):
                 # the chunk's own qptr slice: its offsets stay absolute, into the full candidate arrays
                 ops.explain_curves(params["E"], Kw, S, Wa, ba, params["rel"], h[q0:q1], r[q0:q1], t[q0:q1],
                                    qptr[q0:q1 + 1], crel, ccol, crole, cstep, cval, K, dele[q0:q1], ins[q0:q1])
-            q0 = q1
         return dele, ins
 
 

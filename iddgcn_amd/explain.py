@@ -30,6 +30,7 @@ per-entry state (see the section below).
 ``fidelity_curves`` scores any of their outputs against the model itself: the deletion and insertion curves of each
 triple's explanation, every variant of a triple in one fused kernel (``fidelity_summary``, ``random_explanations``).
 """
+import contextlib
 import time
 
 import numpy as np
@@ -155,8 +156,8 @@ def explaine_batched(model, adjacency_data, test_triples, top_k=10, stats=None):
     n, total = len(triples), dadj.total_nnz
     k = min(int(top_k), total)
     out = eng.value_grads_batch(params, dadj, triples)
-    rel = np.repeat(np.arange(R), dadj.nnz)
-    trip_all = np.stack([np.concatenate(dadj.rows), rel, np.concatenate(dadj.cols)], 1).astype(np.int64)
+    row, col, rel, _ = _entry_table(dadj, real=False)
+    trip_all = np.stack([row, rel, col], 1).astype(np.int64)
     ids = np.zeros((n, k), np.int64)
     scores = np.zeros((n, k), np.float32)
     if n == 0 or k == 0:
@@ -212,9 +213,8 @@ class _ExplaineGraph:
         self.k = min(top_k, dadj.total_nnz)
         self.tr = torch.zeros(3, dtype=torch.int64, device=dev)
         self.ed = _SingleEdge(eng, self.tr)
-        rel = np.repeat(np.arange(dadj.num_relations), dadj.nnz)
-        self.trip_all = torch.as_tensor(np.stack([np.concatenate(dadj.rows), rel, np.concatenate(dadj.cols)], 1),
-                                        device=dev)
+        row, col, rel, _ = _entry_table(dadj, real=False)
+        self.trip_all = torch.as_tensor(np.stack([row, rel, col], 1), device=dev)
         self.eng, self.params, self.dadj = eng, params, dadj
 
         def body():
@@ -377,13 +377,26 @@ def iddgcn_explainer(model, adjacency_data, test_triples, num_epochs=10, learnin
 ROLE_HEAD, ROLE_TAIL = 1, 2      # candidate role bits: the entry's row is h / is t (0: only its column is h or t)
 
 
-def _entry_table(dadj):
+def _entry_table(dadj, real=True):
     """(row, col, rel, real) of every stored entry of ``dadj`` in entry order (host); real = not the (0,0) = 0
-    placeholder of an empty relation."""
+    placeholder of an empty relation (one copy of the values from the device; None with ``real=False``)."""
     row, col = np.concatenate(dadj.rows), np.concatenate(dadj.cols)
     rel = np.repeat(np.arange(dadj.num_relations, dtype=np.int64), dadj.nnz)
-    real = dadj.base_values.cpu().numpy() != 0
-    return row, col, rel, real
+    return row, col, rel, (dadj.base_values.cpu().numpy() != 0) if real else None
+
+
+@contextlib.contextmanager
+def _launch_events(stats):
+    """Brackets a launch sequence with a pair of recorded device events, left in ``stats["launch_events"]`` (nothing
+    when ``stats`` is None)."""
+    if stats is None:
+        yield
+        return
+    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    ev[0].record()
+    yield
+    ev[1].record()
+    stats.update(launch_events=ev)
 
 
 def mask_candidates(dadj, triples):
@@ -480,12 +493,8 @@ def mask_explainer_batched(model, adjacency_data, test_triples, *, num_epochs=5,
     eng, params = _model_state(model)
     N, R = model.num_entities, model.num_relations
     dev = eng.device
-    if eng.node_shard is not None or eng.spmm_shard is not None or eng.row_shard is not None:
-        raise IddgcnError("mask_explainer_batched: not available on a sharded engine: use the per-triple "
-                          "mask_explainer")
-    if eng.D not in (32, 64) or eng.features != "f32" or not 1 <= R <= 8:
-        raise IddgcnError("mask_explainer_batched takes D in {32, 64}, fp32 features and 1 <= R <= 8: use the "
-                          "per-triple mask_explainer for this model")
+    eng.require_per_query("mask_explainer_batched takes D in {32, 64}, fp32 features, 1 <= R <= 8 and an unsharded "
+                          "engine: use the per-triple mask_explainer for this model")
     if target_ratios is not None and len(target_ratios) != R:
         raise IddgcnError("target_ratios needs one entry per relation")
     triples = _as_triples(test_triples)
@@ -506,9 +515,8 @@ def mask_explainer_batched(model, adjacency_data, test_triples, *, num_epochs=5,
     n_levels = int(levels.max()) if Q else 0
     order = np.argsort(levels, kind="stable")
     level_ptr = np.concatenate([[0], np.cumsum(np.bincount(levels, minlength=n_levels + 1)[1:])])
-    row, col, rel_all, _ = _entry_table(dadj)
-
-    g = lambda x, dt: torch.as_tensor(np.ascontiguousarray(x, dtype=dt), device=dev)  # noqa: E731
+    row, col, rel_all, _ = _entry_table(dadj, real=False)
+    g = eng.to_device
     if optimizer is None:
         lr, b1, b2, eps, it0 = learning_rate, 0.9, 0.999, 1e-7, 0
         m = torch.zeros(total, dtype=torch.float32, device=dev)
@@ -523,23 +531,15 @@ def mask_explainer_batched(model, adjacency_data, test_triples, *, num_epochs=5,
     n_steps = Q * num_epochs
     alpha = g(mask_adam_alphas(lr, b1, b2, it0 + 1, n_steps), np.float32)
     out = torch.empty(len(entry), dtype=torch.float32, device=dev)
-    d_qptr, d_entry = g(qptr, np.int64), g(entry, np.int32)
+    d_qptr, d_entry = g(qptr, np.int64), g(entry)
     if Q:
         K, S, Wa, ba = (tuple(params[f"{nm}{l}"] for l in (1, 2, 3)) for nm in ("K", "S", "Wa", "ba"))
         eng.finish_pending()
-        ev = None
-        if stats is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        with eng._mark("mask_explain"):
-            ops.mask_explain(params["E"], K, S, Wa, ba, params["rel"], g(triples[:, 0], np.int32),
-                             g(triples[:, 1], np.int32), g(triples[:, 2], np.int32), d_qptr, d_entry,
-                             g(crel, np.int32), g(ccol, np.int32), g(crole, np.int32), g(init[row, col], np.float32),
-                             m, v, steps, alpha, out, g(order, np.int32), level_ptr, num_epochs, 0, b1, b2, eps,
-                             None if target_ratios is None else g(target_ratios, np.float32))
-        if ev is not None:
-            ev[1].record()
-            stats.update(launch_events=ev)
+        with _launch_events(stats), eng._mark("mask_explain"):
+            ops.mask_explain(params["E"], K, S, Wa, ba, params["rel"], g(triples[:, 0]), g(triples[:, 1]),
+                             g(triples[:, 2]), d_qptr, d_entry, g(crel), g(ccol), g(crole),
+                             g(init[row, col], np.float32), m, v, steps, alpha, out, g(order), level_ptr, num_epochs,
+                             0, b1, b2, eps, None if target_ratios is None else g(target_ratios, np.float32))
     if stats is not None:
         stats.update(levels=n_levels, candidates=int(len(entry)))
     if optimizer is not None:
@@ -721,25 +721,15 @@ def fidelity_curves(model, adjacency_data, test_triples, preds, *, undirected=Fa
     triples = _as_triples(test_triples)
     if len(triples) and (triples[:, 1].min() < 0 or triples[:, 1].max() >= R):
         raise IddgcnError("triple relation index out of range [0, num_relations)")
-    can_fuse = (eng.D in (32, 64) and eng.features == "f32" and 1 <= R <= 8 and eng.node_shard is None and
-                eng.spmm_shard is None and eng.row_shard is None)
-    if fused is None:
-        fused = can_fuse
-    elif fused and not can_fuse:
-        raise IddgcnError("fidelity_curves: the fused kernel takes D in {32, 64}, fp32 features, 1 <= R <= 8 and an "
-                          "unsharded engine: use fused=False for this model")
+    fused = eng.resolve_fused(fused, eng.per_query_ok(),
+                              "fidelity_curves: the fused kernel takes D in {32, 64}, fp32 features, 1 <= R <= 8 and "
+                              "an unsharded engine: use fused=False for this model")
     dadj = DeviceAdjacency(get_adj_mats(adjacency_data, N, R), N, eng.device)
     cand = curve_steps(dadj, triples, preds, undirected)
     K = cand["K"]
     if fused:
-        ev = None
-        if stats is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        dele, ins = eng.edit_curves(params, dadj, triples, cand, K)
-        if ev is not None:
-            ev[1].record()
-            stats.update(launch_events=ev)
+        with _launch_events(stats):
+            dele, ins = eng.edit_curves(params, dadj, triples, cand, K)
     else:
         dele, ins = _curves_layered(eng, params, dadj, triples, cand, K)
     if stats is not None:
@@ -778,7 +768,7 @@ def random_explanations(dadj, triples, k, seed=0):
     if k < 1:
         raise ValueError(f"k must be positive, got {k}")
     qptr, q_of, entry, crel, ccol, _, _ = _row_candidates(dadj, tr)
-    row = np.concatenate(dadj.rows)
+    row = _entry_table(dadj, real=False)[0]
     draw = np.random.default_rng(seed).random(len(entry))
     order = np.lexsort((draw, q_of))                                # a random order inside every triple's segment
     edges = np.stack([row[entry], crel.astype(np.int64), ccol.astype(np.int64)], 1)[order]

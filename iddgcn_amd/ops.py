@@ -18,6 +18,9 @@ from . import _lib as L
 _F32 = torch.float32
 _BF16 = torch.bfloat16
 _I32 = torch.int32
+_I64 = torch.int64
+_U8 = torch.uint8
+_F64 = torch.float64
 
 
 def _ptr(t):
@@ -75,6 +78,88 @@ def _idx_ok(idx, n_rows, bound, name):
             raise L.IddgcnError(f"{name}: index out of range [0, {int(bound)}): min {lo}, max {hi}")
 
 
+def _req_rows(t, shape, name, optional=False):
+    """An fp32 GPU view of the given shape whose rows are contiguous (unit inner stride, row stride = the last dim;
+    the outer strides are free: a node-row range of an (R, N, D) table keeps its relation stride, the engine's
+    ws.P / ws.W / ws.X their layer stride).  Returns the outer strides (elements), zeros for an optional None."""
+    if t is None and optional:
+        return (0,) * (len(shape) - 2)
+    if t is None or not t.is_cuda or t.dtype != _F32:
+        raise L.IddgcnError(f"{name} must be an fp32 GPU tensor (no CPU fallback)")
+    if tuple(t.shape) != tuple(shape) or t.stride(-1) != 1 or t.stride(-2) != shape[-1]:
+        raise L.IddgcnError(f"{name} must be {tuple(shape)} with contiguous rows")
+    return t.stride()[:-2]
+
+
+def _ptr_ascends(p, limit, name, exact=False):
+    """With CHECK_INDEX_RANGES (one host copy): the CSR pointer p ascends within [0, limit], or, ``exact``, from 0
+    to exactly limit."""
+    if not CHECK_INDEX_RANGES or p.numel() < 2:
+        return
+    q = p.cpu()
+    lo, hi = int(q[0]), int(q[-1])
+    if bool((q[1:] < q[:-1]).any()) or ((lo != 0 or hi != limit) if exact else (lo < 0 or hi > limit)):
+        raise L.IddgcnError(f"{name} must ascend " + (f"from 0 to {limit}" if exact else f"within [0, {limit}]"))
+
+
+def _req_layers(K, S, Wa, ba, R, D, who):
+    """The three layers' K (R, D, D), S (D, D), Wa (D, R), ba (R,): fp32 GPU tensors, none missing."""
+    if not (len(K) == len(S) == len(Wa) == len(ba) == 3):
+        raise L.IddgcnError(f"{who}: K, S, Wa, ba must hold the three layers")
+    for l in range(3):
+        for x, shape, nm in ((K[l], (R, D, D), "K"), (S[l], (D, D), "S"), (Wa[l], (D, R), "Wa"), (ba[l], (R,), "ba")):
+            if x is None:
+                raise L.IddgcnError(f"{who}: every layer's K, S, Wa, ba is required ({nm}{l + 1} is None)")
+            _req(x, _F32, shape, f"{nm}{l + 1}")
+
+
+def _req_queries(h, r, t, qptr, crel, ccol, crole, N, R):
+    """The queries (h, r, t) (Q,) of a per-triple kernel and their candidate lists: qptr (Q + 1,) int64 into crel /
+    ccol / crole (C,).  Returns (Q, C)."""
+    Q, C = h.shape[0], crel.shape[0]
+    for idx, n, bound, nm in ((h, Q, N, "h"), (r, Q, R, "r"), (t, Q, N, "t"), (crel, C, R, "crel"), (ccol, C, N, "ccol"),
+                              (crole, C, 4, "crole")):
+        _idx_ok(idx, n, bound, nm)
+    _req(qptr, _I64, (Q + 1,), "qptr")
+    return Q, C
+
+
+def _set_ptrs(a, **fields):
+    """Device pointers into the fields of a MaskExplainArgs / ExplainCurvesArgs: a tensor, None, or the three layers'
+    tensors (the K / S / Wa / ba arrays) per field."""
+    for nm, t in fields.items():
+        if isinstance(t, (list, tuple)):
+            for l in range(3):
+                getattr(a, nm)[l] = t[l].data_ptr()
+        else:
+            setattr(a, nm, None if t is None else t.data_ptr())
+
+
+def _triples3(t, name):
+    _req(t, _I64, None, name)
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise L.IddgcnError(f"{name} must be (n, 3), got {tuple(t.shape)}")
+
+
+def _by_dtype(t, f32, bf16):
+    """The library entry of a pair by the element type of t: ``bf16`` for a bf16 tensor, else ``f32``."""
+    return getattr(L.lib(), bf16 if t.dtype == _BF16 else f32)
+
+
+def _same_size(n, who, **tensors):
+    for nm, t in tensors.items():
+        if t.numel() != n:
+            raise L.IddgcnError(f"{who}: {nm} size mismatch")
+
+
+def _out(t, shape, dtype, device, name):
+    """An output of the given shape and dtype: allocated unless given, a given one checked."""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    _req(t, dtype, shape, name)
+    return t
+
+
 def spmm_csr(row_ptr, col, vals, X, Y, n_seg, n_rows, accumulate=False):
     D = X.shape[1]
     _req(row_ptr, _I32, (n_seg * (n_rows + 1),), "row_ptr")
@@ -102,10 +187,7 @@ def rowgemm(A, B, C, **kw):
     """C = epilogue(A[a_idx] · B^(T)) (include/iddgcn.h, iddgcn_rowgemm_f32); see _rowgemm_args.  bf16 A
     (the bf16-feature mode's edge tables) selects iddgcn_rowgemm_bf16: A, aux and C are then bf16."""
     args = _rowgemm_args(A, B, C, **kw)
-    if A.dtype == _BF16:
-        L.check(L.lib().iddgcn_rowgemm_bf16(_stream(), ctypes.byref(args)), "rowgemm_bf16")
-    else:
-        L.check(L.lib().iddgcn_rowgemm_f32(_stream(), ctypes.byref(args)), "rowgemm")
+    L.check(_by_dtype(A, "iddgcn_rowgemm_f32", "iddgcn_rowgemm_bf16")(_stream(), ctypes.byref(args)), "rowgemm")
 
 
 def rowgemm_kernel_id(A, B, C, **kw):
@@ -214,17 +296,12 @@ def sigma_tn(dO, X, S, dS, slab, precision="exact"):
     _req(S, _F32, (D, D), "S")
     _req(dS, _F32, (D, D), "dS")
     _req(slab, _F32, None, "slab")
-    if et == _BF16:
-        if prec not in (L.GEMM_EXACT_F32, L.GEMM_SPLIT_F16, L.GEMM_BF16X3, L.GEMM_BF16):
-            raise L.IddgcnError(f"sigma_tn: precision {precision!r} is not a form of the bf16 pass")
-        rc = L.lib().iddgcn_sigma_tn_bf16(_stream(), M, D, _ptr(dO), _ptr(X), _ptr(S), _ptr(slab), slab.numel(),
-                                          _ptr(dS), prec)
-    else:
-        if prec != L.GEMM_BF16X3:
-            raise L.IddgcnError(f"sigma_tn: fp32 tables take precision 'bf16x3' only, got {precision!r}")
-        rc = L.lib().iddgcn_sigma_tn_f32(_stream(), M, D, _ptr(dO), _ptr(X), _ptr(S), _ptr(slab), slab.numel(),
-                                         _ptr(dS), prec)
-    L.check(rc, "sigma_tn")
+    if et == _BF16 and prec not in (L.GEMM_EXACT_F32, L.GEMM_SPLIT_F16, L.GEMM_BF16X3, L.GEMM_BF16):
+        raise L.IddgcnError(f"sigma_tn: precision {precision!r} is not a form of the bf16 pass")
+    if et == _F32 and prec != L.GEMM_BF16X3:
+        raise L.IddgcnError(f"sigma_tn: fp32 tables take precision 'bf16x3' only, got {precision!r}")
+    fn = _by_dtype(X, "iddgcn_sigma_tn_f32", "iddgcn_sigma_tn_bf16")
+    L.check(fn(_stream(), M, D, _ptr(dO), _ptr(X), _ptr(S), _ptr(slab), slab.numel(), _ptr(dS), prec), "sigma_tn")
 
 
 def sigma_tn_slab_floats(M, D=256):
@@ -297,7 +374,7 @@ def combine(Y, coef, V, out, *, y_idx=None, coef_idx=None, v_idx=None, v_rel_str
         _req(coef, _F32, (M, R), "coef")
         _idx_ok(y_idx, M, Y.shape[0], "y_idx")
         vrs = V.shape[1] * D if v_rel_stride is None else v_rel_stride
-        fn = L.lib().iddgcn_combine_bf16 if out.dtype == _BF16 else L.lib().iddgcn_combine_planes_f32
+        fn = _by_dtype(out, "iddgcn_combine_planes_f32", "iddgcn_combine_bf16")
         L.check(fn(_stream(), M, D, R, _ptr(Y), _ptr(y_idx), _ptr(coef), _ptr(V), int(vrs), _ptr(out)), "combine_run")
         return
     _req(Y, _F32, None, "Y")
@@ -324,9 +401,8 @@ def distmult_bce(Xh, h_idx, Xt, r_idx, rel, *, t_idx=None, y=None, scale=1.0, p_
     R, D = rel.shape
     _req(h_idx, _I32, (T,), "h_idx")
     _req(r_idx, _I32, (T,), "r_idx")
-    bf = Xt.dtype == _BF16
     _req(Xh, _F32, None, "Xh")
-    _req(Xt, _BF16 if bf else _F32, None, "Xt")
+    _req(Xt, _BF16 if Xt.dtype == _BF16 else _F32, None, "Xt")
     _req(rel, _F32, (R, D), "rel")
     _req(y, _F32, (T,), "y")
     _req(p_out, _F32, (T,), "p_out")
@@ -342,12 +418,10 @@ def distmult_bce(Xh, h_idx, Xt, r_idx, rel, *, t_idx=None, y=None, scale=1.0, p_
         _req(do_out, Xt.dtype, (T, D), "do_out")
         if drel_slab.numel() < nb * R * D or loss_slab.numel() < nb:
             raise L.IddgcnError("distmult slabs too small")
-    fn = L.lib().iddgcn_distmult_bce_bf16 if bf else L.lib().iddgcn_distmult_bce_f32
-    L.check(fn(_stream(), T, D, R, _ptr(Xh), _ptr(h_idx), _ptr(Xt), _ptr(t_idx),
-                                            _ptr(r_idx), _ptr(rel), _ptr(y), float(scale), _ptr(p_out),
-                                            _ptr(s_out), _ptr(ds_out), _ptr(do_out), _ptr(drel_slab), _ptr(loss_slab),
-                                            nb),
-            "distmult_bce")
+    fn = _by_dtype(Xt, "iddgcn_distmult_bce_f32", "iddgcn_distmult_bce_bf16")
+    L.check(fn(_stream(), T, D, R, _ptr(Xh), _ptr(h_idx), _ptr(Xt), _ptr(t_idx), _ptr(r_idx), _ptr(rel), _ptr(y),
+               float(scale), _ptr(p_out), _ptr(s_out), _ptr(ds_out), _ptr(do_out), _ptr(drel_slab), _ptr(loss_slab),
+               nb), "distmult_bce")
     return nb
 
 
@@ -374,11 +448,10 @@ def distmult_bce_heads(seg_ptr, perm, Xh, Xt, r_idx, rel, y, do_out, dXh, drel_s
     nb = distmult_blocks(T)
     if drel_slab.numel() < nb * R * D or loss_slab.numel() < nb:
         raise L.IddgcnError("distmult slabs too small")
-    fn = L.lib().iddgcn_distmult_bce_heads_bf16 if et == _BF16 else L.lib().iddgcn_distmult_bce_heads_f32
-    L.check(fn(_stream(), n_nodes, D, R, _ptr(seg_ptr), _ptr(perm), _ptr(Xh),
-                                                  _ptr(Xt), _ptr(r_idx), _ptr(rel), _ptr(y), float(scale),
-                                                  _ptr(p_out), _ptr(s_out), _ptr(ds_out), _ptr(do_out), _ptr(dXh),
-                                                  _ptr(drel_slab), _ptr(loss_slab), nb), "distmult_bce_heads")
+    fn = _by_dtype(Xt, "iddgcn_distmult_bce_heads_f32", "iddgcn_distmult_bce_heads_bf16")
+    L.check(fn(_stream(), n_nodes, D, R, _ptr(seg_ptr), _ptr(perm), _ptr(Xh), _ptr(Xt), _ptr(r_idx), _ptr(rel),
+               _ptr(y), float(scale), _ptr(p_out), _ptr(s_out), _ptr(ds_out), _ptr(do_out), _ptr(dXh),
+               _ptr(drel_slab), _ptr(loss_slab), nb), "distmult_bce_heads")
     return nb
 
 
@@ -391,18 +464,6 @@ def seg_gather_reduce(seg_ptr, rows, out, *, perm=None, coef=None, r_idx=None, r
             "seg_gather_reduce")
 
 
-def _req_rel_rows(t, shape, name):
-    """An (R, n, D) fp32 GPU view whose rows are contiguous (a node-row range of an (R, N, D) table keeps its
-    relation stride); returns that stride (elements)."""
-    if t is None:
-        return 0
-    if not t.is_cuda or t.dtype != _F32:
-        raise L.IddgcnError(f"{name} must be an fp32 GPU tensor (no CPU fallback)")
-    if tuple(t.shape) != tuple(shape) or t.stride(1) != shape[2] or t.stride(2) != 1:
-        raise L.IddgcnError(f"{name} must be {tuple(shape)} with contiguous rows")
-    return t.stride(0)
-
-
 def tail_seg_reduce_head(seg_ptr, W, dO, P, dP, dWedge, head_dO, Wn, dwh, dsum=None):
     """tail_seg_reduce with per-edge W fused with the head chain's node terms of the same layer: dP[r][n] = tail sum
     + Wn[n][r] head_dO[n], dsum[n] = tail sum + head_dO[n], dwh[n][r] = <head_dO[n], P_r[n]>; the head backward is
@@ -412,19 +473,18 @@ def tail_seg_reduce_head(seg_ptr, W, dO, P, dP, dWedge, head_dO, Wn, dwh, dsum=N
     matching slice of the tail pointers, absolute edge offsets)."""
     R, n_nodes, D = P.shape
     _req(seg_ptr, _I32, (n_nodes + 1,), "seg_ptr")
-    ps = _req_rel_rows(P, (R, n_nodes, D), "P")
-    dps = _req_rel_rows(dP, (R, n_nodes, D), "dP")
+    ps, = _req_rows(P, (R, n_nodes, D), "P")
+    dps, = _req_rows(dP, (R, n_nodes, D), "dP", optional=True)
     _req(dsum, _F32, (n_nodes, D), "dsum")
     _req(head_dO, _F32, (n_nodes, D), "head_dO")
     _req(Wn, _F32, (n_nodes, R), "Wn")
     _req(dwh, _F32, (n_nodes, R), "dwh")
-    bf = dO.dtype == _BF16
-    _req(dO, _BF16 if bf else _F32, None, "dO")
+    _req(dO, _BF16 if dO.dtype == _BF16 else _F32, None, "dO")
     _req(W, _F32, None, "W")
     _req(dWedge, _F32, None, "dWedge")
     if W.shape[0] != dO.shape[0]:
         raise L.IddgcnError("tail_seg_reduce_head: per-edge W must have one row per edge")
-    fn = L.lib().iddgcn_tail_seg_reduce_head_bf16 if bf else L.lib().iddgcn_tail_seg_reduce_head_f32
+    fn = _by_dtype(dO, "iddgcn_tail_seg_reduce_head_f32", "iddgcn_tail_seg_reduce_head_bf16")
     L.check(fn(_stream(), n_nodes, D, R, _ptr(seg_ptr), _ptr(W), _ptr(dO), _ptr(P), ps, _ptr(dP), dps, _ptr(dsum),
                _ptr(dWedge), _ptr(head_dO), _ptr(Wn), _ptr(dwh)), "tail_seg_reduce_head")
 
@@ -448,16 +508,15 @@ def tail_seg_reduce(seg_ptr, h_idx, W, dO, P, dP, dWedge, dsum=None):
     D) views with contiguous rows (a node-row range: seg_ptr the matching slice of the tail pointers)."""
     R, n_nodes, D = P.shape
     _req(seg_ptr, _I32, (n_nodes + 1,), "seg_ptr")
-    ps = _req_rel_rows(P, (R, n_nodes, D), "P")
-    dps = _req_rel_rows(dP, (R, n_nodes, D), "dP")
+    ps, = _req_rows(P, (R, n_nodes, D), "P")
+    dps, = _req_rows(dP, (R, n_nodes, D), "dP", optional=True)
     _req(dsum, _F32, (n_nodes, D), "dsum")
     if h_idx is None and W.shape[0] != dO.shape[0]:
         raise L.IddgcnError("tail_seg_reduce: per-edge W must have one row per edge")
     _req(dO, _BF16 if dO.dtype == _BF16 else _F32, None, "dO")
-    fn = L.lib().iddgcn_tail_seg_reduce_bf16 if dO.dtype == _BF16 else L.lib().iddgcn_tail_seg_reduce_f32
-    L.check(fn(_stream(), n_nodes, D, R, _ptr(seg_ptr), _ptr(h_idx), _ptr(W),
-                                               _ptr(dO), _ptr(P), ps, _ptr(dP), dps, _ptr(dsum),
-                                               _ptr(dWedge)), "tail_seg_reduce")
+    fn = _by_dtype(dO, "iddgcn_tail_seg_reduce_f32", "iddgcn_tail_seg_reduce_bf16")
+    L.check(fn(_stream(), n_nodes, D, R, _ptr(seg_ptr), _ptr(h_idx), _ptr(W), _ptr(dO), _ptr(P), ps, _ptr(dP), dps,
+               _ptr(dsum), _ptr(dWedge)), "tail_seg_reduce")
 
 
 def head_bwd_node(dO, P, Ssm, W, dP, dz, *, hseg_ptr=None, hperm=None, dWedge=None, dsum=None, ep=None):
@@ -471,15 +530,12 @@ def head_bwd_node(dO, P, Ssm, W, dP, dz, *, hseg_ptr=None, hperm=None, dWedge=No
     _req(dz, _F32, (n_nodes, R), "dz")
     _req(dsum, _F32, (n_nodes, D), "dsum")
     _req(ep, _F32, (n_nodes, R), "ep")
-    for t, nm in ((P, "P"), (dP, "dP")):
-        if t is None:             # dP None (ABI 9): its head term was added by tail_seg_reduce_head
-            continue
-        if tuple(t.shape) != (R, n_nodes, D) or t.stride(1) != D or t.stride(2) != 1:
-            raise L.IddgcnError(f"head_bwd_node: {nm} must be (R, n, D) with contiguous rows")
-    L.check(L.lib().iddgcn_head_bwd_node_f32(_stream(), n_nodes, D, R, _ptr(dO), _ptr(P), P.stride(0), _ptr(Ssm),
-                                             _ptr(W), _ptr(hseg_ptr), _ptr(hperm), _ptr(dWedge), _ptr(ep), _ptr(dP),
-                                             dP.stride(0) if dP is not None else 0, _ptr(dsum), _ptr(dz)),
-            "head_bwd_node")
+    ps, = _req_rows(P, (R, n_nodes, D), "P")
+    # dP None (ABI 9): its head term was added by tail_seg_reduce_head
+    dps, = _req_rows(dP, (R, n_nodes, D), "dP", optional=True)
+    L.check(L.lib().iddgcn_head_bwd_node_f32(_stream(), n_nodes, D, R, _ptr(dO), _ptr(P), ps, _ptr(Ssm), _ptr(W),
+                                             _ptr(hseg_ptr), _ptr(hperm), _ptr(dWedge), _ptr(ep), _ptr(dP), dps,
+                                             _ptr(dsum), _ptr(dz)), "head_bwd_node")
 
 
 def head_wsum(hptr, hperm, w, out):
@@ -512,9 +568,7 @@ def reduce_slabs(slab, n_slabs, out, accumulate=False, scale=1.0):
 
 def adam(var, m, v, g, alpha, b1, b2, eps, sparse_form):
     n = var.numel()
-    for t, nm in ((m, "m"), (v, "v"), (g, "g")):
-        if t.numel() != n:
-            raise L.IddgcnError(f"adam: {nm} size mismatch")
+    _same_size(n, "adam", m=m, v=v, g=g)
     L.check(L.lib().iddgcn_adam_f32(_stream(), n, _ptr(var), _ptr(m), _ptr(v), _ptr(g), float(alpha), float(b1),
                                     float(b2), float(eps), int(sparse_form)), "adam")
 
@@ -522,9 +576,7 @@ def adam(var, m, v, g, alpha, b1, b2, eps, sparse_form):
 def adam_table(var, m, v, g, alpha_table, step, b1, b2, eps, sparse_form):
     """iddgcn_adam_f32 with alpha = alpha_table[step[0]] read on the device (graph-replayable)."""
     n = var.numel()
-    for t, nm in ((m, "m"), (v, "v"), (g, "g")):
-        if t.numel() != n:
-            raise L.IddgcnError(f"adam: {nm} size mismatch")
+    _same_size(n, "adam", m=m, v=v, g=g)
     _req(alpha_table, _F32, None, "alpha_table")
     _req(step, _I32, (1,), "step")
     L.check(L.lib().iddgcn_adam_table_f32(_stream(), n, _ptr(var), _ptr(m), _ptr(v), _ptr(g), _ptr(alpha_table),
@@ -539,10 +591,6 @@ def step_advance(step, loss_history=None, loss=None):
 
 
 # -- device graph build (include/iddgcn_graph.h) ------------------------------------------------
-_I64 = torch.int64
-_U8 = torch.uint8
-
-
 def _workspace(nbytes, device):
     if nbytes < 0:
         raise L.IddgcnError("graph build: sizes out of range")
@@ -572,9 +620,7 @@ def build_adjacency(triples, N, R):
     """utils1.get_adj_mats + DeviceAdjacency's CSR layouts on the GPU.  triples: (M, 3) int64 GPU
     tensor.  Returns a dict of GPU tensors (capacity M + R) and the host counts
     (nnz, placeholders, error)."""
-    _req(triples, _I64, None, "triples")
-    if triples.dim() != 2 or triples.shape[1] != 3:
-        raise L.IddgcnError(f"triples must be (M, 3), got {tuple(triples.shape)}")
+    _triples3(triples, "triples")
     M = triples.shape[0]
     dev = triples.device
     need = L.lib().iddgcn_adjacency_workspace(M, N, R)
@@ -598,9 +644,7 @@ def build_adjacency(triples, N, R):
 def build_scored_edges(triples, labels, N, R):
     """graph.ScoredEdges on the GPU: tail-sorted (stable) h/r/t, gathered labels, tptr, hperm, hptr,
     inv.  Returns (dict of GPU tensors, error flag)."""
-    _req(triples, _I64, None, "triples")
-    if triples.dim() != 2 or triples.shape[1] != 3:
-        raise L.IddgcnError(f"triples must be (T, 3), got {tuple(triples.shape)}")
+    _triples3(triples, "triples")
     T = triples.shape[0]
     dev = triples.device
     _req(labels, _F32, (T,), "labels")
@@ -622,7 +666,7 @@ def build_scored_edges(triples, labels, N, R):
 def similarity_pairs(X, threshold, capacity=None, band_capacity=None):
     """Keys i*N + j (unordered, int64 GPU tensor) of every i < j with cosine(X_i, X_j) > threshold.
     X: (N, F) float64 GPU tensor.  Reruns once with exact buffer sizes if a capacity was short."""
-    _req(X, torch.float64, None, "X")
+    _req(X, _F64, None, "X")
     if X.dim() != 2:
         raise L.IddgcnError("X must be (N, F)")
     N, F = X.shape
@@ -667,9 +711,7 @@ def negative_samples(triples, num_entities, seed):
     """utils1.generate_negative_samples_np (utils1.py:646-655) on the GPU, bit-exact: triples (M, 3)
     int64 GPU tensor -> (M, 3) int64 negatives.  Host synchronisations: one per round of entity words
     (normally one)."""
-    _req(triples, _I64, None, "triples")
-    if triples.dim() != 2 or triples.shape[1] != 3:
-        raise L.IddgcnError(f"triples must be (M, 3), got {tuple(triples.shape)}")
+    _triples3(triples, "triples")
     N = int(num_entities)
     if not 1 <= N <= 2 ** 31 - 1:
         raise L.IddgcnError("num_entities must be in [1, 2^31)")
@@ -719,15 +761,6 @@ def planes_to_f32(t):
     return ((h[:, :, 0].float() + h[:, :, 1].float()) * PLANE_INV).reshape(t.shape[0], t.shape[1])
 
 
-def f32_to_planes(x):
-    """The planes encoding of values in [0, 1] (round-to-nearest-even fp16 casts), as the producers write it."""
-    xs = x.float() * 2.0 ** 15
-    hi = xs.half()
-    lo = (xs - hi.float()).half()
-    rows = x.shape[0]
-    return torch.stack([hi.view(rows, -1, 32), lo.view(rows, -1, 32)], 2).reshape(rows, -1).contiguous().view(torch.float32)
-
-
 # -- all-candidate ranking (include/iddgcn_screen.h) ---------------------------------------------
 _SIDES = {"tail": L.SCREEN_TAIL, "head": L.SCREEN_HEAD, L.SCREEN_TAIL: L.SCREEN_TAIL, L.SCREEN_HEAD: L.SCREEN_HEAD}
 
@@ -751,19 +784,16 @@ def screen_chain(q_node, q_rel, ES1, P, W, X3, S2, S3, rel, s, side="tail"):
     for t, shape, nm in ((ES1, (N, D), "ES1"), (X3, (N, D), "X3"), (S2, (D, D), "S2"), (S3, (D, D), "S3"),
                          (rel, (R, D), "rel")):
         _req(t, _F32, shape, nm)
-    for t, shape, nm in ((P, (3, R, N, D), "P"), (W, (3, N, R), "W")):
-        if t is None or not t.is_cuda or t.dtype != _F32:
-            raise L.IddgcnError(f"{nm} must be an fp32 GPU tensor (no CPU fallback)")
-        if tuple(t.shape) != shape or t.stride(-1) != 1 or t.stride(-2) != shape[-1]:
-            raise L.IddgcnError(f"{nm} must be {shape} with contiguous rows")
-    if P.stride(1) < N * D:
+    ps0, ps1 = _req_rows(P, (3, R, N, D), "P")
+    ws0, = _req_rows(W, (3, N, R), "W")
+    if ps1 < N * D:
         raise L.IddgcnError("screen_chain: the relations of P overlap")
     # rows of ES1 and P are read as 16-byte vectors
-    if (ES1.data_ptr() | P.data_ptr()) & 15 or P.stride(0) % 4 or P.stride(1) % 4:
+    if (ES1.data_ptr() | P.data_ptr()) & 15 or ps0 % 4 or ps1 % 4:
         raise L.IddgcnError("screen_chain: ES1 / P must be 16-byte aligned, P's layer and relation strides "
                             "multiples of 4 floats")
     L.check(L.lib().iddgcn_screen_chain_f32(_stream(), Q, N, D, R, _side(side), _ptr(q_node), _ptr(q_rel), _ptr(ES1),
-                                            _ptr(P), P.stride(0), P.stride(1), _ptr(W), W.stride(0), _ptr(X3),
+                                            _ptr(P), ps0, ps1, _ptr(W), ws0, _ptr(X3),
                                             _ptr(S2), _ptr(S3), _ptr(rel), _ptr(s)), "screen_chain")
 
 
@@ -791,34 +821,19 @@ def rank_topk(s, target, k, fptr=None, fidx=None, greater=None, equal=None, topk
     if fptr is not None:
         _req(fptr, _I32, (Q + 1,), "fptr")
         _req(fidx, _I32, None, "fidx")
-        if CHECK_INDEX_RANGES and Q:
-            p = fptr.cpu()
-            if int(p[0]) < 0 or bool((p[1:] < p[:-1]).any()) or int(p[-1]) > fidx.numel():
-                raise L.IddgcnError("rank_topk: fptr must ascend within [0, len(fidx)]")
+        _ptr_ascends(fptr, fidx.numel(), "rank_topk: fptr")
         if fidx.numel() == 0:
             fptr = fidx = None
-    greater = torch.empty(Q, dtype=_I32, device=dev) if greater is None else greater
-    equal = torch.empty(Q, dtype=_I32, device=dev) if equal is None else equal
-    topk_idx = torch.empty(Q, k, dtype=_I32, device=dev) if topk_idx is None else topk_idx
-    topk_val = torch.empty(Q, k, dtype=_F32, device=dev) if topk_val is None else topk_val
-    _req(greater, _I32, (Q,), "greater")
-    _req(equal, _I32, (Q,), "equal")
-    _req(topk_idx, _I32, (Q, k), "topk_idx")
-    _req(topk_val, _F32, (Q, k), "topk_val")
+    greater = _out(greater, (Q,), _I32, dev, "greater")
+    equal = _out(equal, (Q,), _I32, dev, "equal")
+    topk_idx = _out(topk_idx, (Q, k), _I32, dev, "topk_idx")
+    topk_val = _out(topk_val, (Q, k), _F32, dev, "topk_val")
     L.check(L.lib().iddgcn_rank_topk_f32(_stream(), Q, N, k, _ptr(s), _ptr(target), _ptr(fptr), _ptr(fidx),
                                          _ptr(greater), _ptr(equal), _ptr(topk_idx), _ptr(topk_val)), "rank_topk")
     return greater, equal, topk_idx, topk_val
 
 
 # -- batched explaiNE (include/iddgcn_explain.h) ---------------------------------------------------
-def _layered(t, shape, nm):
-    """A (3, ..) fp32 GPU view whose layers are contiguous blocks of rows (the engine's ws.P / ws.W / ws.X)."""
-    if t is None or not t.is_cuda or t.dtype != _F32:
-        raise L.IddgcnError(f"{nm} must be an fp32 GPU tensor (no CPU fallback)")
-    if tuple(t.shape) != shape or t.stride(-1) != 1 or t.stride(-2) != shape[-1]:
-        raise L.IddgcnError(f"{nm} must be {shape} with contiguous rows")
-
-
 def explain_seeds(h, r, t, ES1, P, W, Ssm, X, K, S2, S3, Wa2, Wa3, rel, scale=1.0, G=None, p=None):
     """dAE rows of Q predictions (iddgcn_explain_seeds_f32; D in {32, 64}, fp32 tables): for query q = (h[q], r[q],
     t[q]) the tail chain is recomputed from the node tables and the backward of ``scale * p_q`` gives
@@ -840,24 +855,22 @@ def explain_seeds(h, r, t, ES1, P, W, Ssm, X, K, S2, S3, Wa2, Wa3, rel, scale=1.
         if x is None:
             raise L.IddgcnError(f"explain_seeds: {nm} is required")
         _req(x, _F32, shape, nm)
-    _layered(P, (3, R, N, D), "P")
-    _layered(W, (3, N, R), "W")
-    _layered(Ssm, (3, N, R), "Ssm")
-    _layered(X, (3, N, D), "X")
-    if P.stride(1) < N * D:
+    ps0, ps1 = _req_rows(P, (3, R, N, D), "P")
+    ws0, = _req_rows(W, (3, N, R), "W")
+    ss0, = _req_rows(Ssm, (3, N, R), "Ssm")
+    xs0, = _req_rows(X, (3, N, D), "X")
+    if ps1 < N * D:
         raise L.IddgcnError("explain_seeds: the relations of P overlap")
-    if W.stride(0) != Ssm.stride(0):
+    if ws0 != ss0:
         raise L.IddgcnError("explain_seeds: W and Ssm must share their layer stride")
-    G = torch.empty(Q, 2, R, D, dtype=_F32, device=ES1.device) if G is None else G
-    p = torch.empty(Q, dtype=_F32, device=ES1.device) if p is None else p
-    _req(G, _F32, (Q, 2, R, D), "G")
-    _req(p, _F32, (Q,), "p")
-    if (ES1.data_ptr() | P.data_ptr() | G.data_ptr()) & 15 or P.stride(0) % 4 or P.stride(1) % 4:
+    G = _out(G, (Q, 2, R, D), _F32, ES1.device, "G")
+    p = _out(p, (Q,), _F32, ES1.device, "p")
+    if (ES1.data_ptr() | P.data_ptr() | G.data_ptr()) & 15 or ps0 % 4 or ps1 % 4:
         raise L.IddgcnError("explain_seeds: ES1 / P / G must be 16-byte aligned, P's layer and relation strides "
                             "multiples of 4 floats")
     L.check(L.lib().iddgcn_explain_seeds_f32(
-        _stream(), Q, N, D, R, _ptr(h), _ptr(r), _ptr(t), float(scale), _ptr(ES1), _ptr(P), P.stride(0), P.stride(1),
-        _ptr(W), _ptr(Ssm), W.stride(0), _ptr(X), X.stride(0), _ptr(K[0]), _ptr(K[1]), _ptr(K[2]), _ptr(S2), _ptr(S3),
+        _stream(), Q, N, D, R, _ptr(h), _ptr(r), _ptr(t), float(scale), _ptr(ES1), _ptr(P), ps0, ps1,
+        _ptr(W), _ptr(Ssm), ws0, _ptr(X), xs0, _ptr(K[0]), _ptr(K[1]), _ptr(K[2]), _ptr(S2), _ptr(S3),
         _ptr(Wa2), _ptr(Wa3), _ptr(rel), _ptr(G), _ptr(p)), "explain_seeds")
     return G, p
 
@@ -876,19 +889,16 @@ def explain_row_grads(h, t, row_ptr, col, G, E, qptr, entry, grad, entry_of_csr=
     _idx_ok(t, Q, N, "t")
     _req(row_ptr, _I32, (R * (N + 1),), "row_ptr")
     _req(col, _I32, None, "col")
-    _req(qptr, torch.int64, (Q + 1,), "qptr")
+    _req(qptr, _I64, (Q + 1,), "qptr")
     _req(entry, _I32, None, "entry")
     _req(grad, _F32, None, "grad")
     if entry.dim() != 1 or grad.shape != entry.shape:
         raise L.IddgcnError("explain_row_grads: entry and grad must be 1-d and of one length")
     if entry_of_csr is not None:
-        _req(entry_of_csr, torch.int64, (col.shape[0],), "entry_of_csr")
+        _req(entry_of_csr, _I64, (col.shape[0],), "entry_of_csr")
     if (E.data_ptr() | G.data_ptr()) & 15:
         raise L.IddgcnError("explain_row_grads: E / G must be 16-byte aligned")
-    if CHECK_INDEX_RANGES and Q:
-        qp = qptr.cpu()
-        if int(qp[0]) < 0 or bool((qp[1:] < qp[:-1]).any()) or int(qp[-1]) > entry.numel():
-            raise L.IddgcnError("explain_row_grads: qptr must ascend within [0, len(entry)]")
+    _ptr_ascends(qptr, entry.numel(), "explain_row_grads: qptr")
     L.check(L.lib().iddgcn_explain_row_grads_f32(
         _stream(), Q, N, D, R, _ptr(h), _ptr(t), _ptr(row_ptr), _ptr(col), _ptr(entry_of_csr), _ptr(G), _ptr(E),
         _ptr(qptr), _ptr(entry), _ptr(grad)), "explain_row_grads")
@@ -901,7 +911,7 @@ def explain_topk(qptr, entry, grad, k, topk_entry=None, topk_val=None, n_pos=Non
     k = int(k)
     if not 1 <= k <= L.TOPK_MAX:
         raise L.IddgcnError(f"explain_topk: k must be in [1, {L.TOPK_MAX}]")
-    _req(qptr, torch.int64, None, "qptr")
+    _req(qptr, _I64, None, "qptr")
     if qptr.dim() != 1 or qptr.shape[0] < 1:
         raise L.IddgcnError("explain_topk: qptr must be (Q + 1,)")
     Q = qptr.shape[0] - 1
@@ -909,17 +919,11 @@ def explain_topk(qptr, entry, grad, k, topk_entry=None, topk_val=None, n_pos=Non
     _req(grad, _F32, None, "grad")
     if entry.dim() != 1 or grad.shape != entry.shape:
         raise L.IddgcnError("explain_topk: entry and grad must be 1-d and of one length")
-    if CHECK_INDEX_RANGES and Q:
-        qp = qptr.cpu()
-        if int(qp[0]) < 0 or bool((qp[1:] < qp[:-1]).any()) or int(qp[-1]) > entry.numel():
-            raise L.IddgcnError("explain_topk: qptr must ascend within [0, len(entry)]")
+    _ptr_ascends(qptr, entry.numel(), "explain_topk: qptr")
     dev = qptr.device
-    topk_entry = torch.empty(Q, k, dtype=_I32, device=dev) if topk_entry is None else topk_entry
-    topk_val = torch.empty(Q, k, dtype=_F32, device=dev) if topk_val is None else topk_val
-    n_pos = torch.empty(Q, dtype=_I32, device=dev) if n_pos is None else n_pos
-    _req(topk_entry, _I32, (Q, k), "topk_entry")
-    _req(topk_val, _F32, (Q, k), "topk_val")
-    _req(n_pos, _I32, (Q,), "n_pos")
+    topk_entry = _out(topk_entry, (Q, k), _I32, dev, "topk_entry")
+    topk_val = _out(topk_val, (Q, k), _F32, dev, "topk_val")
+    n_pos = _out(n_pos, (Q,), _I32, dev, "n_pos")
     L.check(L.lib().iddgcn_explain_topk_f32(_stream(), Q, k, _ptr(qptr), _ptr(entry), _ptr(grad), _ptr(topk_entry),
                                             _ptr(topk_val), _ptr(n_pos)), "explain_topk")
     return topk_entry, topk_val, n_pos
@@ -939,31 +943,15 @@ def mask_explain(E, K, S, Wa, ba, rel, h, r, t, qptr, entry, crel, ccol, crole, 
     D in {32, 64}, 1 <= R <= 8.  Index values are the caller's to validate (IDDGCN_CHECK_INDICES=1 checks them here)."""
     N, D = E.shape
     R = rel.shape[0]
-    Q = h.shape[0]
     num_epochs, epochs_base = int(num_epochs), int(epochs_base)
     if num_epochs < 0 or epochs_base < 0:
         raise L.IddgcnError("mask_explain: num_epochs and epochs_base must be non-negative")
     _req(E, _F32, (N, D), "E")
     _req(rel, _F32, (R, D), "rel")
-    if not (len(K) == len(S) == len(Wa) == len(ba) == 3):
-        raise L.IddgcnError("mask_explain: K, S, Wa, ba must hold the three layers")
-    for l in range(3):
-        _req(K[l], _F32, (R, D, D), f"K{l + 1}")
-        _req(S[l], _F32, (D, D), f"S{l + 1}")
-        _req(Wa[l], _F32, (D, R), f"Wa{l + 1}")
-        _req(ba[l], _F32, (R,), f"ba{l + 1}")
-        if K[l] is None or S[l] is None or Wa[l] is None or ba[l] is None:
-            raise L.IddgcnError("mask_explain: every layer's K, S, Wa, ba is required")
-    _idx_ok(h, Q, N, "h")
-    _idx_ok(r, Q, R, "r")
-    _idx_ok(t, Q, N, "t")
-    _req(qptr, torch.int64, (Q + 1,), "qptr")
-    C = entry.shape[0]
+    _req_layers(K, S, Wa, ba, R, D, "mask_explain")
+    Q, C = _req_queries(h, r, t, qptr, crel, ccol, crole, N, R)
     total = m.shape[0]
     _idx_ok(entry, C, total, "entry")
-    _idx_ok(crel, C, R, "crel")
-    _idx_ok(ccol, C, N, "ccol")
-    _idx_ok(crole, C, 4, "crole")
     _req(init_e, _F32, (total,), "init_e")
     _req(m, _F32, (total,), "m")
     _req(v, _F32, (total,), "v")
@@ -981,26 +969,16 @@ def mask_explain(E, K, S, Wa, ba, rel, h, r, t, qptr, entry, crel, ccol, crole, 
         raise L.IddgcnError("mask_explain: level_ptr must ascend within [0, len(qids)]")
     if E.data_ptr() & 15:
         raise L.IddgcnError("mask_explain: E must be 16-byte aligned")
-    if CHECK_INDEX_RANGES and Q:
-        qp = qptr.cpu()
-        if int(qp[0]) != 0 or bool((qp[1:] < qp[:-1]).any()) or int(qp[-1]) != C:
-            raise L.IddgcnError("mask_explain: qptr must ascend from 0 to len(entry)")
+    _ptr_ascends(qptr, C, "mask_explain: qptr", exact=True)
     a = L.MaskExplainArgs()
     a.N, a.d, a.R, a.num_epochs, a.epochs_base = N, D, R, num_epochs, epochs_base
-    a.h, a.r, a.t, a.qptr = h.data_ptr(), r.data_ptr(), t.data_ptr(), qptr.data_ptr()
-    a.entry, a.crel, a.ccol, a.crole = entry.data_ptr(), crel.data_ptr(), ccol.data_ptr(), crole.data_ptr()
-    a.E, a.rel = E.data_ptr(), rel.data_ptr()
+    a.b1, a.b2, a.eps = float(b1), float(b2), float(eps)
     # the backward reads K^l_r^T and S^l^T along rows: transposed copies, made once per call
     KT = [x.transpose(1, 2).contiguous() for x in K]
     ST = [x.t().contiguous() for x in S]
-    for l in range(3):
-        a.K[l], a.S[l], a.Wa[l], a.ba[l] = K[l].data_ptr(), S[l].data_ptr(), Wa[l].data_ptr(), ba[l].data_ptr()
-        a.KT[l], a.ST[l] = KT[l].data_ptr(), ST[l].data_ptr()
-    a.init_e, a.m, a.v, a.steps, a.alpha = init_e.data_ptr(), m.data_ptr(), v.data_ptr(), steps.data_ptr(), \
-        alpha.data_ptr()
-    a.b1, a.b2, a.eps = float(b1), float(b2), float(eps)
-    a.target_ratios = None if target_ratios is None else target_ratios.data_ptr()
-    a.out = out.data_ptr()
+    _set_ptrs(a, h=h, r=r, t=t, qptr=qptr, entry=entry, crel=crel, ccol=ccol, crole=crole, E=E, rel=rel, K=K, KT=KT,
+              S=S, ST=ST, Wa=Wa, ba=ba, init_e=init_e, m=m, v=v, steps=steps, alpha=alpha, target_ratios=target_ratios,
+              out=out)
     fn, st = L.lib().iddgcn_mask_explain_f32, _stream()
     for lo, hi in zip(lp, lp[1:]):
         if hi == lo:
@@ -1021,64 +999,32 @@ def explain_curves(E, K, S, Wa, ba, rel, h, r, t, qptr, crel, ccol, crole, cstep
     caller's to validate (IDDGCN_CHECK_INDICES=1 checks them here)."""
     N, D = E.shape
     R = rel.shape[0]
-    Q = h.shape[0]
     k = int(k)
     if not 1 <= k <= L.TOPK_MAX:
         raise L.IddgcnError(f"explain_curves: k must be in [1, {L.TOPK_MAX}]")
     _req(E, _F32, (N, D), "E")
     _req(rel, _F32, (R, D), "rel")
-    if not (len(K) == len(S) == len(Wa) == len(ba) == 3):
-        raise L.IddgcnError("explain_curves: K, S, Wa, ba must hold the three layers")
-    for l in range(3):
-        if K[l] is None or S[l] is None or Wa[l] is None or ba[l] is None:
-            raise L.IddgcnError("explain_curves: every layer's K, S, Wa, ba is required")
-        _req(K[l], _F32, (R, D, D), f"K{l + 1}")
-        _req(S[l], _F32, (D, D), f"S{l + 1}")
-        _req(Wa[l], _F32, (D, R), f"Wa{l + 1}")
-        _req(ba[l], _F32, (R,), f"ba{l + 1}")
-    _idx_ok(h, Q, N, "h")
-    _idx_ok(r, Q, R, "r")
-    _idx_ok(t, Q, N, "t")
-    _req(qptr, torch.int64, (Q + 1,), "qptr")
-    C = crel.shape[0]
-    _idx_ok(crel, C, R, "crel")
-    _idx_ok(ccol, C, N, "ccol")
-    _idx_ok(crole, C, 4, "crole")
+    _req_layers(K, S, Wa, ba, R, D, "explain_curves")
+    Q, C = _req_queries(h, r, t, qptr, crel, ccol, crole, N, R)
     _req(cstep, _I32, (C,), "cstep")
     _req(cval, _F32, (C,), "cval")
     dev = E.device
-    deletion = torch.empty(Q, k + 1, dtype=_F32, device=dev) if deletion is None else deletion
-    insertion = torch.empty(Q, k + 1, dtype=_F32, device=dev) if insertion is None else insertion
-    _req(deletion, _F32, (Q, k + 1), "deletion")
-    _req(insertion, _F32, (Q, k + 1), "insertion")
+    deletion = _out(deletion, (Q, k + 1), _F32, dev, "deletion")
+    insertion = _out(insertion, (Q, k + 1), _F32, dev, "insertion")
     if E.data_ptr() & 15:
         raise L.IddgcnError("explain_curves: E must be 16-byte aligned")
-    if CHECK_INDEX_RANGES and Q:
-        qp = qptr.cpu()
-        if int(qp[0]) < 0 or bool((qp[1:] < qp[:-1]).any()) or int(qp[-1]) > C:
-            raise L.IddgcnError("explain_curves: qptr must ascend within [0, len(crel)]")
-        if C and (int(cstep.min()) < -1 or int(cstep.max()) >= k):
-            raise L.IddgcnError("explain_curves: cstep must lie in [-1, k)")
+    _ptr_ascends(qptr, C, "explain_curves: qptr")
+    if CHECK_INDEX_RANGES and Q and C and (int(cstep.min()) < -1 or int(cstep.max()) >= k):
+        raise L.IddgcnError("explain_curves: cstep must lie in [-1, k)")
     a = L.ExplainCurvesArgs()
     a.N, a.d, a.R, a.k, a.Q = N, D, R, k, Q
-    a.h, a.r, a.t, a.qptr = h.data_ptr(), r.data_ptr(), t.data_ptr(), qptr.data_ptr()
-    a.crel, a.ccol, a.crole, a.cstep, a.cval = crel.data_ptr(), ccol.data_ptr(), crole.data_ptr(), \
-        cstep.data_ptr(), cval.data_ptr()
-    a.E, a.rel = E.data_ptr(), rel.data_ptr()
-    for l in range(3):
-        a.K[l], a.S[l], a.Wa[l], a.ba[l] = K[l].data_ptr(), S[l].data_ptr(), Wa[l].data_ptr(), ba[l].data_ptr()
-    a.del_, a.ins = deletion.data_ptr(), insertion.data_ptr()
+    _set_ptrs(a, h=h, r=r, t=t, qptr=qptr, crel=crel, ccol=ccol, crole=crole, cstep=cstep, cval=cval, E=E, rel=rel,
+              K=K, S=S, Wa=Wa, ba=ba, del_=deletion, ins=insertion)
     L.check(L.lib().iddgcn_explain_curves_f32(_stream(), ctypes.byref(a)), "explain_curves")
     return deletion, insertion
 
 
 # -- explanation ground truth (include/iddgcn_ground_truth.h) ------------------------------------
-def _triples3(t, name):
-    _req(t, _I64, None, name)
-    if t.dim() != 2 or t.shape[1] != 3:
-        raise L.IddgcnError(f"{name} must be (n, 3), got {tuple(t.shape)}")
-
-
 def gt_sim_lists(sim, N):
     """Similarity lists of every node as a CSR (ptr [N+1], val [2n], first [2n]) and the device error flag (not
     read here).  sim: (n, 3) int64 GPU tensor."""
@@ -1156,9 +1102,6 @@ def ground_truth_fill(queries, mu, drug, dc, N, R, ptr, total, drug_rel, mu_rel)
 
 
 # -- classification metrics on the device (include/iddgcn_metrics.h) -----------------------------
-_F64 = torch.float64
-
-
 def clf_metrics_workspace(n, G, device):
     """The workspace tensor iddgcn_clf_metrics needs for n elements and G groups (one byte at the least)."""
     nbytes = L.lib().iddgcn_clf_metrics_workspace(int(n), int(G))
