@@ -78,6 +78,18 @@ class ExplainCurvesArgs(ctypes.Structure):
     ]
 
 
+class CounterfactualArgs(ctypes.Structure):
+    """Mirror of iddgcn_counterfactual_t (include/iddgcn_explain.h)."""
+    _fields_ = [
+        ("N", ci), ("d", ci), ("R", ci), ("k", ci), ("Q", ci), ("mode", ci), ("threshold", cf), ("max_cand", ci),
+        ("h", vp), ("r", vp), ("t", vp), ("qptr", vp),
+        ("crel", vp), ("ccol", vp), ("crole", vp), ("cpartner", vp), ("celig", vp), ("cval", vp),
+        ("E", vp), ("K", vp * 3), ("S", vp * 3), ("Wa", vp * 3), ("ba", vp * 3), ("rel", vp),
+        ("path", vp), ("chosen", vp), ("cstep", vp), ("n_steps", vp), ("flipped", vp), ("loo", vp), ("scratch", vp),
+    ]
+
+
+CF_FLIP, CF_LOWER, CF_RAISE = 0, 1, 2             # include/iddgcn_explain.h IDDGCN_CF_*
 TN_BATCH = 4
 SCREEN_TAIL, SCREEN_HEAD = 0, 1                   # include/iddgcn_screen.h IDDGCN_SCREEN_*
 TOPK_MAX = 64
@@ -157,6 +169,8 @@ SIGNATURES = {
     "iddgcn_mask_explain_f32": (ci, [vp, ctypes.POINTER(MaskExplainArgs)]),
     # deletion / insertion curves of explanations (added symbol only)
     "iddgcn_explain_curves_f32": (ci, [vp, ctypes.POINTER(ExplainCurvesArgs)]),
+    # greedy counterfactual search and the occlusion table (added symbol only)
+    "iddgcn_explain_counterfactual_f32": (ci, [vp, ctypes.POINTER(CounterfactualArgs)]),
     # include/iddgcn_ground_truth.h (explanation ground truth; added symbols only)
     "iddgcn_gt_sim_lists_workspace": (ci, [cll, ctypes.POINTER(cll)]),
     "iddgcn_gt_sim_lists": (ci, [vp, cll, ci, vp, vp, vp, vp, vp, vp, cll]),

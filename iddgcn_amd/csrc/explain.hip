@@ -18,7 +18,9 @@
 //
 // mask_explain_kernel (further down): every epoch of one triple's mask training in one workgroup.
 //
-// curves_kernel (last): the deletion and insertion curves of an explanation, a tile of edited forwards per workgroup.
+// curves_kernel: the deletion and insertion curves of an explanation, a tile of edited forwards per workgroup.
+//
+// cf_step_kernel / cf_select_kernel (last): the greedy counterfactual search, one pair of launches per step.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -933,6 +935,242 @@ __global__ __launch_bounds__(NT) void curves_kernel(const iddgcn_explain_curves_
     }
 }
 
+// ---- counterfactual search -------------------------------------------------------------------------------------
+// cf_step_kernel: curves_kernel's sibling for step `step` of the greedy search: same staging, same AE chains, same
+// forward (written out again: curves_kernel keeps its machine code), another keep predicate.  With F the candidates
+// removed so far (cstep >= 0; nothing at step 0, where cstep is not read), variant 0 is F itself and variant 1 + j
+// drops candidate j and its partner too.  A variant is stored when it is the base at step 0 (path[q][0]) or an
+// eligible candidate outside F (vals[j]); the others are computed and dropped.  Workgroup b of a query's `tiles` takes
+// the tiles b, b + tiles, .. of 8 variants, so the E rows are staged once and the grid need not know the segment's
+// length.  LDS: curves_kernel's 152.5 KB at D = 64 and nothing more (the variant table lives in registers).
+template <int D>
+__global__ __launch_bounds__(NT) void cf_step_kernel(const iddgcn_counterfactual_t a, int step, int tiles,
+                                                     float* __restrict__ vals) {
+    constexpr int GR = NT / D;
+    constexpr int RPG = MAX_R / GR;
+    constexpr int RW = CV_ROWS / GR;
+    constexpr int ES_ROWS = CV_ES_BYTES / (4 * D);
+    __shared__ float es[ES_ROWS * D];
+    __shared__ __attribute__((aligned(16))) float AE[MAX_R][CV_ROWS][D];
+    __shared__ float P[MAX_R][CV_ROWS][D];
+    __shared__ __attribute__((aligned(16))) float x[2][CV_ROWS][D];
+    __shared__ float zs[CV_VT][MAX_R];
+    __shared__ float w[CV_VT][MAX_R];
+    __shared__ int rstart[MAX_R + 1];
+
+    const int tid = threadIdx.x;
+    const int R = a.R;
+    const int q = blockIdx.x / tiles;
+    // a query that has stopped: flipped, or the step before this one was not taken
+    if (step > 0 && (a.flipped[q] || a.n_steps[q] != step)) return;
+    const int hh = a.h[q], rr = a.r[q], tt = a.t[q];
+    const long long c0 = a.qptr[q];
+    const int n = (int)(a.qptr[q + 1] - c0);
+    const int nv = n + 1;
+    const int* crel = a.crel + c0;
+    const int* ccol = a.ccol + c0;
+    const int* crole = a.crole + c0;
+    const int* cpartner = a.cpartner + c0;
+    const int* celig = a.celig + c0;
+    const int* cstep = a.cstep + c0;
+    const float* cval = a.cval + c0;
+    const int k = tid % D, grp = tid / D;
+    bool staged = false;
+
+    for (int v0 = (blockIdx.x % tiles) * CV_VT; v0 < nv; v0 += tiles * CV_VT) {
+        // variants past the last repeat it (computed, never stored); jv: the candidate a variant drops, -1: none
+        int jv[CV_VT], pv[CV_VT];
+        bool store[CV_VT];
+        bool any = false;
+#pragma unroll
+        for (int u = 0; u < CV_VT; ++u) {
+            const int vi = v0 + u < nv ? v0 + u : nv - 1;
+            jv[u] = vi - 1;
+            pv[u] = -1;
+            store[u] = false;
+            if (v0 + u < nv) {
+                if (vi == 0) {
+                    store[u] = step == 0;
+                } else {
+                    pv[u] = cpartner[vi - 1];
+                    store[u] = celig[vi - 1] != 0 && (step == 0 || cstep[vi - 1] < 0);
+                }
+            }
+            any = any || store[u];
+        }
+        if (!any) continue;                    // uniform over the workgroup
+
+        if (!staged) {
+            // the relation segments of the candidate list and the staged E rows
+            if (tid <= MAX_R) rstart[tid] = n;
+            __syncthreads();
+            for (int j = tid; j < n; j += NT) {
+                const int r1 = crel[j];
+                const int r0 = j ? crel[j - 1] : -1;
+                for (int r = r0 + 1; r <= r1; ++r) rstart[r] = j;
+            }
+            const int ns = n < ES_ROWS ? n : ES_ROWS;
+            for (int idx = tid; idx < ns * D; idx += NT) es[idx] = a.E[(size_t)ccol[idx / D] * D + idx % D];
+            staged = true;
+        }
+        // x^0 = E[h] / E[t] in every variant (the last tile's readers of x are past a barrier)
+        for (int idx = tid; idx < CV_ROWS * D; idx += NT) {
+            const int row = idx / D;
+            x[0][row][idx % D] = a.E[(size_t)((row & 1) ? tt : hh) * D + idx % D];
+        }
+        __syncthreads();
+
+        // AE rows of every variant: curves_kernel's chains, a dropped candidate enters with a zero multiplier
+#pragma unroll
+        for (int ri = 0; ri < RPG; ++ri) {
+            const int r = grp + ri * GR;
+            if (r < R) {
+                float acc[CV_ROWS];
+#pragma unroll
+                for (int j = 0; j < CV_ROWS; ++j) acc[j] = 0.f;
+                const int j1 = rstart[r + 1];
+                for (int j = rstart[r]; j < j1; ++j) {
+                    const float val = cval[j];
+                    const int role = crole[j];
+                    const bool gone = step > 0 && cstep[j] >= 0;
+                    const float ev = j < ES_ROWS ? es[j * D + k] : a.E[(size_t)ccol[j] * D + k];
+                    const float vh = (role & 1) ? val : 0.f, vt = (role & 2) ? val : 0.f;
+#pragma unroll
+                    for (int u = 0; u < CV_VT; ++u) {
+                        const bool keep = !gone && j != jv[u] && j != pv[u];
+                        acc[2 * u] = fmaf(keep ? vh : 0.f, ev, acc[2 * u]);
+                        acc[2 * u + 1] = fmaf(keep ? vt : 0.f, ev, acc[2 * u + 1]);
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < CV_ROWS; ++j) AE[r][j][k] = acc[j];
+            }
+        }
+        __syncthreads();
+
+        // forward: the reference layer on the CV_ROWS rows, as in curves_kernel
+        for (int l = 0; l < 3; ++l) {
+            const int cur = l & 1;
+            for (int item = grp; item < CV_VT * R; item += GR) {
+                const int u = item / R, r = item % R;
+                const float z = group_sum<D>(x[cur][2 * u][k] * a.Wa[l][(size_t)k * R + r]);
+                if (k == 0) zs[u][r] = z + a.ba[l][r];
+            }
+#pragma unroll
+            for (int ri = 0; ri < RPG; ++ri) {
+                const int r = grp + ri * GR;
+                if (r < R) {
+                    float y[CV_ROWS];
+                    matvec_rows<D, CV_ROWS>(a.K[l] + (size_t)r * D * D + k, &AE[r][0][0], D, y);
+#pragma unroll
+                    for (int j = 0; j < CV_ROWS; ++j) P[r][j][k] = y[j];
+                }
+            }
+            __syncthreads();
+            if (tid < CV_VT * R) {
+                const int u = tid / R, r = tid % R;
+                float mx = -INFINITY;
+                for (int i = 0; i < R; ++i) mx = fmaxf(mx, zs[u][i]);
+                float sum = 0.f;
+                for (int i = 0; i < R; ++i) sum += expf(zs[u][i] - mx);
+                w[u][r] = sigmoid_ref(expf(zs[u][r] - mx) / sum);
+            }
+            __syncthreads();
+            {
+                float y[RW];
+                matvec_rows<D, RW>(a.S[l] + k, &x[cur][grp * RW][0], D, y);
+#pragma unroll
+                for (int j = 0; j < RW; ++j) {
+                    const int row = grp * RW + j;
+                    float v = y[j];
+                    for (int r = 0; r < R; ++r) v = fmaf(w[row >> 1][r], P[r][row][k], v);
+                    x[1 - cur][row][k] = sigmoid_ref(v);
+                }
+            }
+            __syncthreads();
+        }
+
+        // DistMult of every variant (x^3 sits in x[1])
+        for (int u = grp; u < CV_VT; u += GR) {
+            const float s = group_sum<D>(x[1][2 * u][k] * a.rel[(size_t)rr * D + k] * x[1][2 * u + 1][k]);
+            if (k == 0 && store[u]) {
+                if (jv[u] < 0)
+                    a.path[(size_t)q * (a.k + 1)] = sigmoid_ref(s);
+                else
+                    vals[c0 + jv[u]] = sigmoid_ref(s);
+            }
+        }
+        __syncthreads();                       // x[1] is read above, x[0] rewritten by the next tile
+    }
+}
+
+// the candidate of the smallest dir * p first, equal bit patterns: the lowest index (p is a sigmoid: never negative)
+__device__ __forceinline__ unsigned long long cf_key(float p, int lower, int j) {
+    const unsigned u = __float_as_uint(p);
+    return ((unsigned long long)(lower ? u : ~u) << 32) | (unsigned)j;
+}
+
+// cf_select_kernel: one workgroup per query, step `step` (choose = 0: K = 0, only the bookkeeping of step 0).
+__global__ __launch_bounds__(NT) void cf_select_kernel(const iddgcn_counterfactual_t a, int step, int choose,
+                                                       const float* __restrict__ vals) {
+    __shared__ unsigned long long best[NT];
+    const int tid = threadIdx.x;
+    const int q = blockIdx.x;
+    const int K = a.k;
+    const long long c0 = a.qptr[q];
+    const int n = (int)(a.qptr[q + 1] - c0);
+    float* path = a.path + (size_t)q * (K + 1);
+    const float p0 = path[0];
+    const float thr = a.threshold;
+    const int lower = a.mode == IDDGCN_CF_LOWER || (a.mode == IDDGCN_CF_FLIP && p0 > thr);
+    int active;
+    if (step == 0) {
+        active = lower ? p0 > thr : !(p0 > thr);           // not yet on the target side
+        for (int j = tid; j < n; j += NT) {
+            a.cstep[c0 + j] = -1;
+            if (!a.celig[c0 + j]) a.loo[c0 + j] = __int_as_float(0x7fc00000);
+        }
+    } else {
+        active = !a.flipped[q] && a.n_steps[q] == step;
+    }
+    unsigned long long key = ~0ull;
+    if (active && choose)
+        for (int j = tid; j < n; j += NT)
+            if (a.celig[c0 + j] && (step == 0 || a.cstep[c0 + j] < 0)) {
+                const unsigned long long kj = cf_key(vals[c0 + j], lower, j);
+                key = kj < key ? kj : key;
+            }
+    best[tid] = key;
+    __syncthreads();                                       // also orders step 0's cstep = -1 before the choice's writes
+    for (int s = NT / 2; s > 0; s >>= 1) {
+        if (tid < s && best[tid + s] < best[tid]) best[tid] = best[tid + s];
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    key = best[0];
+    const bool take = key != ~0ull;                        // an eligible candidate was left
+    if (take) {
+        const int j = (int)(unsigned)key;
+        const float p = vals[c0 + j];
+        const int pj = a.cpartner[c0 + j];
+        a.cstep[c0 + j] = step;
+        if (pj >= 0 && pj < n) a.cstep[c0 + pj] = step;
+        a.chosen[(size_t)q * K + step] = j;
+        path[step + 1] = p;
+        a.n_steps[q] = step + 1;
+        a.flipped[q] = lower ? !(p > thr) : p > thr;
+    } else {
+        if (choose) {
+            a.chosen[(size_t)q * K + step] = -1;
+            path[step + 1] = path[step];
+        }
+        if (step == 0) {
+            a.n_steps[q] = 0;
+            a.flipped[q] = !active;
+        }
+    }
+}
+
 }  // namespace xpl
 
 extern "C" {
@@ -1044,6 +1282,37 @@ int iddgcn_explain_curves_f32(void* stream, const iddgcn_explain_curves_t* args)
     for_small_width(a.d, [&](auto D) {
         hipLaunchKernelGGL(curves_kernel<decltype(D)::value>, grid, dim3(NT), 0, (hipStream_t)stream, a, n_tiles);
     });
+    return (int)hipGetLastError();
+}
+
+int iddgcn_explain_counterfactual_f32(void* stream, const iddgcn_counterfactual_t* args) {
+    using namespace xpl;
+    if (!args) return IDDGCN_E_BAD_ARG;
+    const iddgcn_counterfactual_t& a = *args;
+    if (a.d != 32 && a.d != 64) return IDDGCN_E_BAD_DIM;
+    if (a.R < 1 || a.R > MAX_R) return IDDGCN_E_BAD_REL;
+    if (a.k < 0 || a.k > IDDGCN_TOPK_MAX || a.Q < 0 || a.N < 1 || a.max_cand < 0) return IDDGCN_E_BAD_ARG;
+    if (a.mode != IDDGCN_CF_FLIP && a.mode != IDDGCN_CF_LOWER && a.mode != IDDGCN_CF_RAISE) return IDDGCN_E_BAD_ARG;
+    if (a.Q == 0) return 0;
+    if (!a.h || !a.r || !a.t || !a.qptr || !a.E || !a.rel || !a.path || !a.n_steps || !a.flipped ||
+        (a.k > 0 && !a.chosen) || (a.k > 1 && a.loo && !a.scratch))
+        return IDDGCN_E_BAD_ARG;
+    // the per-candidate arrays may be null when every segment is empty: they are then never touched
+    if (!layers_ok(a.K, a.S, a.Wa, a.ba)) return IDDGCN_E_BAD_ARG;
+    if ((uintptr_t)a.E & 15) return IDDGCN_E_BAD_ARG;
+    long long tiles = ((long long)a.max_cand + 1 + CV_VT - 1) / CV_VT;
+    tiles = tiles > 1024 ? 1024 : tiles;
+    if ((long long)a.Q * tiles > 0x7fffffffLL) return IDDGCN_E_BAD_ARG;
+    const dim3 grid((unsigned)(a.Q * tiles));
+    const hipStream_t st = (hipStream_t)stream;
+    const int steps = a.k > 0 ? a.k : 1;
+    for (int i = 0; i < steps; ++i) {
+        float* vals = i == 0 ? a.loo : a.scratch;
+        for_small_width(a.d, [&](auto D) {
+            hipLaunchKernelGGL(cf_step_kernel<decltype(D)::value>, grid, dim3(NT), 0, st, a, i, (int)tiles, vals);
+        });
+        hipLaunchKernelGGL(cf_select_kernel, dim3((unsigned)a.Q), dim3(NT), 0, st, a, i, a.k > 0 ? 1 : 0, vals);
+    }
     return (int)hipGetLastError();
 }
 

@@ -1373,6 +1373,76 @@ class Engine:
                                    qptr[q0:q1 + 1], crel, ccol, crole, cstep, cval, K, dele[q0:q1], ins[q0:q1])
         return dele, ins
 
+    def counterfactual_search(self, params, adj, triples, cand, K, toward="flip", threshold=0.5,
+                              max_entries=1 << 22):
+        """The greedy counterfactual search of Q triples and their occlusion tables (ops.explain_counterfactual):
+        per chunk 2 max(K, 1) launches with every decision taken on the device.
+
+        ``cand``: explain.counterfactual_candidates' dict over ``adj`` (host arrays ``qptr``, ``rel``, ``col``,
+        ``role``, ``val``, ``partner``, ``eligible``).  0 <= K <= 64 (0: only the occlusion table and p).  The queries
+        run in chunks of at most ``max_entries`` candidates, at least one query each.  fp32 features with D in
+        {32, 64}, 1 <= R <= 8, unsharded engine: IddgcnError otherwise (explain.counterfactual_batched(fused=False)
+        covers the rest).  Returns a dict of device tensors: ``path`` (Q, K + 1), ``chosen`` (Q, K) int32, ``n_steps``,
+        ``flipped`` (Q,) int32, ``cstep`` int32 and ``loo`` fp32 per candidate."""
+        self.require_per_query("counterfactual_search takes D in {32, 64}, fp32 features, 1 <= R <= 8 and an "
+                               "unsharded engine: use explain.counterfactual_batched(fused=False) for this engine")
+        N, R, dev = self.N, self.R, self.device
+        K = int(K)
+        if not 0 <= K <= L.TOPK_MAX:
+            raise L.IddgcnError(f"counterfactual_search: K must be in [0, {L.TOPK_MAX}], got {K}")
+        if adj.num_entities != N or adj.num_relations != R:
+            raise L.IddgcnError("counterfactual_search: the adjacency is not this engine's size")
+        if int(max_entries) < 1:
+            raise ValueError(f"max_entries must be positive, got {max_entries}")
+        q = self._triples(triples, "triples", "triple")
+        Q = q.shape[0]
+        qp = np.asarray(cand["qptr"], np.int64)
+        C = len(cand["rel"])
+        if qp.shape != (Q + 1,) or qp[0] != 0 or qp[-1] != C or (np.diff(qp) < 0).any():
+            raise L.IddgcnError("counterfactual_search: cand['qptr'] must be (Q + 1,), ascending from 0 to the "
+                                "candidate count")
+        if any(len(cand[nm]) != C for nm in ("col", "role", "val", "partner", "eligible")):
+            raise L.IddgcnError("counterfactual_search: the candidate arrays must be of one length")
+        deg = np.diff(qp)
+        if C:
+            rel, col, role, part = (np.asarray(cand[nm]) for nm in ("rel", "col", "role", "partner"))
+            inner = np.ones(C, bool)
+            inner[qp[:-1][qp[:-1] < C]] = False                    # a segment's first candidate has no predecessor
+            has = part >= 0
+            at = np.repeat(qp[:-1], deg) + np.where(has, part, 0)  # the partner's absolute place
+            if (rel.min() < 0 or rel.max() >= R or col.min() < 0 or col.max() >= N or role.min() < 1 or
+                    role.max() > 3 or part.min() < -1 or (part >= np.repeat(deg, deg)).any() or
+                    (np.diff(rel)[inner[1:]] < 0).any()):
+                raise L.IddgcnError("counterfactual_search: candidate out of range (rel, col, role in 1..3, partner "
+                                    "in [-1, n)) or relations not ascending inside a query")
+            if (part[at[has]] != (np.arange(C) - np.repeat(qp[:-1], deg))[has]).any():
+                raise L.IddgcnError("counterfactual_search: partner must be symmetric")
+        g = self.to_device
+        out = dict(path=torch.empty(Q, K + 1, dtype=torch.float32, device=dev),
+                   chosen=torch.empty(Q, K, dtype=torch.int32, device=dev),
+                   n_steps=torch.empty(Q, dtype=torch.int32, device=dev),
+                   flipped=torch.empty(Q, dtype=torch.int32, device=dev),
+                   cstep=torch.empty(C, dtype=torch.int32, device=dev),
+                   loo=torch.empty(C, dtype=torch.float32, device=dev))
+        if Q == 0:
+            return out
+        scratch = torch.empty(C, dtype=torch.float32, device=dev)
+        h, r, t, qptr = g(q[:, 0]), g(q[:, 1]), g(q[:, 2]), g(qp, np.int64)
+        crel, ccol, crole, cpart = (g(cand[nm]) for nm in ("rel", "col", "role", "partner"))
+        celig = g(np.asarray(cand["eligible"]).astype(np.int32))
+        cval = g(cand["val"], np.float32)
+        Kw, S, Wa, ba = (tuple(params[f"{nm}{l}"] for l in (1, 2, 3)) for nm in ("K", "S", "Wa", "ba"))
+        self.finish_pending()
+        for q0, q1 in self._query_chunks(qp, max_entries):
+            with self._mark("counterfactual_search"):
+                # the chunk's own qptr slice: its offsets stay absolute, into the full candidate arrays
+                ops.explain_counterfactual(params["E"], Kw, S, Wa, ba, params["rel"], h[q0:q1], r[q0:q1], t[q0:q1],
+                                           qptr[q0:q1 + 1], crel, ccol, crole, cpart, celig, cval, K, toward,
+                                           threshold, int(deg[q0:q1].max()), out["path"][q0:q1],
+                                           out["chosen"][q0:q1], out["cstep"], out["n_steps"][q0:q1],
+                                           out["flipped"][q0:q1], out["loo"], scratch)
+        return out
+
 
 def step_flops(N, R, D, T, M):
     """Algorithmic work of one training step (W_gemm)."""

@@ -29,6 +29,9 @@ per-entry state (see the section below).
 
 ``fidelity_curves`` scores any of their outputs against the model itself: the deletion and insertion curves of each
 triple's explanation, every variant of a triple in one fused kernel (``fidelity_summary``, ``random_explanations``).
+
+``counterfactual_batched`` optimises what those curves measure: a greedy search for the few edges whose removal flips
+a prediction, every decision on the device; ``occlusion_batched`` ranks edges by their exact leave-one-out effect.
 """
 import contextlib
 import time
@@ -773,6 +776,252 @@ def random_explanations(dadj, triples, k, seed=0):
     order = np.lexsort((draw, q_of))                                # a random order inside every triple's segment
     edges = np.stack([row[entry], crel.astype(np.int64), ccol.astype(np.int64)], 1)[order]
     return [edges[qptr[q]:min(qptr[q] + k, qptr[q + 1])] for q in range(len(tr))]
+
+
+# -- counterfactual edge sets and occlusion scores ---------------------------------------------------
+# Which few edges, if they were not in the graph, would change this call?  The deterministic answer to the question
+# the deletion curve measures: remove the most damaging candidate, re-evaluate, repeat until the prediction crosses
+# the threshold (include/iddgcn_explain.h has the exact rules).  Step 0's table is the exact leave-one-out change of
+# the probability for every edge the prediction can see (occlusion_batched).  Every p(F) is the deletion forward of
+# fidelity_curves, bit for bit, so a returned edge list's deletion curve IS the search's path.
+def counterfactual_candidates(dadj, triples, undirected=False, exclude_target=False, relations=None):
+    """curve_steps' candidates of each triple with the search's two per-candidate rules (host).
+
+    ``partner``: with ``undirected``, candidate (i, rel, c) and candidate (c, rel, i) of the same triple are removed
+    together — the segment-relative index of the other one, -1 when there is none (always when i == c); both are
+    candidates only when i and c both lie in {h, t}.  ``eligible``: False for the entries (h, r, t) / (t, r, h) with
+    ``exclude_target`` and for every relation outside ``relations`` (None: all) — such a candidate stays in the graph
+    and is never evaluated.  Returns a dict of host arrays: ``qptr`` (n + 1,) int64; per candidate ``entry``, ``rel``,
+    ``col``, ``role``, ``row``, ``partner`` (int32), ``val`` (fp32) and ``eligible`` (bool)."""
+    tr = _as_triples(triples)
+    n, N, R = len(tr), dadj.num_entities, dadj.num_relations
+    qptr, q_of, entry, crel, ccol, crole, val = _row_candidates(dadj, tr)
+    crow = _entry_table(dadj, real=False)[0][entry]
+    C = len(entry)
+    within = np.arange(C) - qptr[:-1][q_of]
+    partner = np.full(C, -1, np.int64)
+    if undirected and C:
+        # (triple, rel, row, col) -> candidate: the lists ascend by (triple, entry id) = (triple, rel, row, col)
+        key = ((q_of * R + crel) * N + crow) * N + ccol
+        want = ((q_of * R + crel) * N + ccol) * N + crow
+        at = np.minimum(np.searchsorted(key, want), C - 1)
+        hit = (key[at] == want) & (at != np.arange(C))
+        partner[hit] = within[at[hit]]
+    eligible = np.ones(C, bool)
+    if exclude_target and C:
+        h, r, t = (tr[q_of, c] for c in range(3))
+        eligible &= ~((crel == r) & (((crow == h) & (ccol == t)) | ((crow == t) & (ccol == h))))
+    if relations is not None:
+        rels = np.asarray(list(relations), np.int64).reshape(-1)
+        if len(rels) and (rels.min() < 0 or rels.max() >= R):
+            raise IddgcnError("relations: index out of range [0, num_relations)")
+        eligible &= np.isin(crel, rels)
+    i32 = np.int32
+    return dict(qptr=qptr, entry=entry.astype(i32), rel=crel.astype(i32), col=ccol.astype(i32),
+                role=crole.astype(i32), row=crow.astype(i32), partner=partner.astype(i32), val=val,
+                eligible=eligible)
+
+
+def _lowering(p0, toward, threshold):
+    """The search's direction per triple from the unedited fp32 probabilities: True lowers p, False raises it."""
+    if toward not in ops.CF_MODES:
+        raise IddgcnError(f"toward must be 'flip', 'lower' or 'raise', got {toward!r}")
+    p0 = np.asarray(p0, np.float32)
+    if toward == "flip":
+        return p0 > np.float32(threshold)
+    return np.full(p0.shape, toward == "lower")
+
+
+def _counterfactual_layered(eng, params, dadj, triples, cand, K, toward, threshold):
+    """The search with one set_values + Engine.predict per evaluated variant and the kernels' rules on the host (any
+    width and mode): the fused route's cross-check and its timing baseline.  Host arrays, counterfactual_search's
+    keys."""
+    base = dadj.base_values.to(torch.float32)
+    n, qp, thr = len(triples), cand["qptr"], np.float32(threshold)
+    C = len(cand["entry"])
+    out = dict(path=np.zeros((n, K + 1), np.float32), chosen=np.full((n, K), -1, np.int32),
+               n_steps=np.zeros(n, np.int32), flipped=np.zeros(n, np.int32), cstep=np.full(C, -1, np.int32),
+               loo=np.full(C, np.nan, np.float32))
+    entry = torch.as_tensor(cand["entry"].astype(np.int64), device=eng.device)
+    for q in range(n):
+        ed = eng.edges(triples[q][None])
+        a, b = int(qp[q]), int(qp[q + 1])
+        e, part, elig = entry[a:b], cand["partner"][a:b], cand["eligible"][a:b]
+        gone = np.zeros(b - a, bool)
+
+        def p_without(extra):
+            drop = gone.copy()
+            drop[list(extra)] = True
+            vals = base.clone()
+            vals[e[torch.as_tensor(np.flatnonzero(drop), device=eng.device)]] = 0
+            dadj.set_values(vals)
+            return np.float32(eng.predict(params, dadj, ed)[0].item())
+
+        p = p_without(())
+        out["path"][q] = p
+        lower = bool(_lowering(p, toward, threshold))
+        crossed = lambda v: (not v > thr) if lower else bool(v > thr)  # noqa: E731
+        with_partner = lambda j: [j] + ([part[j]] if part[j] >= 0 else [])  # noqa: E731
+        live = np.flatnonzero(elig)
+        pj = np.array([p_without(with_partner(j)) for j in live], np.float32)
+        out["loo"][a + live] = pj
+        for i in range(K):
+            if crossed(p) or not len(live):
+                break
+            if i > 0:
+                pj = np.array([p_without(with_partner(j)) for j in live], np.float32)
+            best = int(np.lexsort((live, pj if lower else -pj))[0])
+            j, p = int(live[best]), pj[best]
+            gone[with_partner(j)] = True
+            out["cstep"][a + np.flatnonzero(gone & (out["cstep"][a:b] < 0))] = i
+            out["chosen"][q, i], out["path"][q, i + 1:], out["n_steps"][q] = j, p, i + 1
+            live = np.flatnonzero(elig & ~gone)
+        out["flipped"][q] = crossed(p)
+    dadj.set_values(base)
+    return out
+
+
+def _counterfactual_run(model, adjacency_data, test_triples, K, toward, threshold, undirected, exclude_target,
+                        relations, fused, stats):
+    """The shared body of counterfactual_batched and occlusion_batched: (triples, dadj, cand, result, fused, eng)."""
+    eng, params = _model_state(model)
+    N, R = model.num_entities, model.num_relations
+    triples = _as_triples(test_triples)
+    if len(triples) and (triples[:, 1].min() < 0 or triples[:, 1].max() >= R):
+        raise IddgcnError("triple relation index out of range [0, num_relations)")
+    if not 0 <= K <= TOPK_MAX:
+        raise IddgcnError(f"the search takes between 0 and {TOPK_MAX} steps, got {K}")
+    _lowering(0.0, toward, threshold)
+    fused = eng.resolve_fused(fused, eng.per_query_ok(),
+                              "counterfactual search: the fused kernels take D in {32, 64}, fp32 features, "
+                              "1 <= R <= 8 and an unsharded engine: use fused=False for this model")
+    dadj = DeviceAdjacency(get_adj_mats(adjacency_data, N, R), N, eng.device)
+    cand = counterfactual_candidates(dadj, triples, undirected, exclude_target, relations)
+    if fused:
+        with _launch_events(stats):
+            res = eng.counterfactual_search(params, dadj, triples, cand, K, toward, threshold)
+    else:
+        res = _counterfactual_layered(eng, params, dadj, triples, cand, K, toward, threshold)
+    if stats is not None:
+        stats.update(fused=bool(fused), candidates=int(len(cand["entry"])))
+    return triples, dadj, cand, res, fused, eng
+
+
+def _candidate_edges(cand):
+    return np.stack([cand["row"], cand["rel"], cand["col"]], 1).astype(np.int64)
+
+
+def counterfactual_batched(model, adjacency_data, test_triples, max_edges=10, *, toward="flip", threshold=0.5,
+                           undirected=False, exclude_target=False, relations=None, fused=None,
+                           return_occlusion=False, stats=None):
+    """Per test triple, a small set of stored edges whose removal moves the prediction across ``threshold``, found by
+    greedy deletion: at every step each remaining eligible candidate (counterfactual_candidates) is removed in turn on
+    top of those already gone, and the one that leaves the smallest probability (largest when raising; equal values:
+    the lowest entry id) goes — even when nothing improves.  The search stops when the prediction has crossed the
+    threshold (a triple already on the target side takes no step), after ``max_edges`` steps (0 .. 64) or when no
+    eligible candidate is left.  No random numbers; every probability is fidelity_curves' deletion forward bit for bit.
+
+    ``toward``: "flip" lowers p where p > threshold and raises it elsewhere; "lower" / "raise" fix the direction.
+    ``undirected``: an edge between h and t goes together with its stored reverse, as one step.  ``exclude_target``:
+    never remove (h, r, t) / (t, r, h) themselves; ``relations``: only remove edges of these relations.  ``fused``:
+    None takes the kernels (Engine.counterfactual_search) for fp32 features, D in {32, 64}, R <= 8 and an unsharded
+    engine; False runs one set_values + predict per evaluated variant (any width); True demands the kernels.
+    ``stats``: an optional dict that receives ``fused``, ``candidates`` and, fused, ``launch_events``.
+
+    Returns a dict: ``p`` (n,) the unedited predictions; ``direction`` (n,) +1 where the search lowers p, -1 where it
+    raises it; ``edges``: a list of (n_edges[q], 3) int64 (head, rel, tail) arrays in removal order, ready for
+    fidelity_curves (same ``undirected``) and evaluate_explanations; ``path`` (n, max_edges + 1): the probability after
+    0, 1, .. removals, repeating its last value past the end — the deletion curve of ``edges``; ``chosen``
+    (n, max_edges) the candidate index of each step, -1 padded; ``n_edges`` (n,); ``flipped`` (n,) bool; with
+    ``return_occlusion``, ``occlusion``: a list of (candidates, 3) edge arrays and a list of the probabilities with
+    each one removed alone (NaN: not eligible), per triple."""
+    K = int(max_edges)
+    triples, dadj, cand, res, fused, eng = _counterfactual_run(model, adjacency_data, test_triples, K, toward,
+                                                               threshold, undirected, exclude_target, relations,
+                                                               fused, stats)
+    res = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in res.items()}
+    qp, edges_of = cand["qptr"], _candidate_edges(cand)
+    n_steps = res["n_steps"].astype(np.int64)
+    out = dict(p=res["path"][:, 0].copy(),
+               direction=np.where(_lowering(res["path"][:, 0], toward, threshold), 1, -1).astype(np.int64),
+               edges=[edges_of[qp[q] + res["chosen"][q, :n_steps[q]].astype(np.int64)] for q in range(len(triples))],
+               path=res["path"], chosen=res["chosen"], n_edges=n_steps, flipped=res["flipped"].astype(bool))
+    if return_occlusion:
+        out["occlusion"] = ([edges_of[qp[q]:qp[q + 1]] for q in range(len(triples))],
+                            [res["loo"][qp[q]:qp[q + 1]] for q in range(len(triples))])
+    return out
+
+
+def occlusion_batched(model, adjacency_data, test_triples, top_k=10, *, toward="flip", threshold=0.5,
+                      undirected=False, exclude_target=False, relations=None, fused=None, stats=None):
+    """Occlusion scores as an explainer: per test triple the ``top_k`` (1 .. 64) eligible candidates whose removal
+    alone moves the prediction most in the search's direction.  The score of candidate j is p - p(without j) when
+    lowering and its negative when raising — exact, one edited forward per candidate; descending, ties by ascending
+    entry id (ops.explain_topk on the fused route).  The selection keywords are counterfactual_batched's.  Returns the
+    explainers' (list of (k_q, 3) int64 (head, rel, tail) arrays, list of (k_q,) fp32 scores), k_q = min(top_k,
+    eligible candidates)."""
+    k = int(top_k)
+    if not 1 <= k <= TOPK_MAX:
+        raise IddgcnError(f"top_k must be in [1, {TOPK_MAX}], got {top_k}")
+    triples, dadj, cand, res, fused, eng = _counterfactual_run(model, adjacency_data, test_triples, 0, toward,
+                                                               threshold, undirected, exclude_target, relations,
+                                                               fused, stats)
+    n, qp, edges_of = len(triples), cand["qptr"], _candidate_edges(cand)
+    q_of = np.repeat(np.arange(n), np.diff(qp))
+    if fused:
+        dev = eng.device
+        p0 = res["path"][:, 0]
+        sign = torch.as_tensor(np.where(_lowering(p0.cpu().numpy(), toward, threshold), 1.0, -1.0).astype(np.float32),
+                               device=dev)
+        qd = torch.as_tensor(q_of, device=dev)
+        score = torch.where(torch.as_tensor(cand["eligible"], device=dev), sign[qd] * (p0[qd] - res["loo"]),
+                            torch.full_like(res["loo"], -np.inf))
+        with eng._mark("occlusion_topk"):
+            te, tv, _ = ops.explain_topk(eng.to_device(qp, np.int64), eng.to_device(cand["entry"]), score, k)
+        te, tv = te.cpu().numpy().astype(np.int64), tv.cpu().numpy()
+        # entry id -> candidate: the segments ascend by entry id
+        total = dadj.total_nnz
+        ckey = q_of.astype(np.int64) * total + cand["entry"]
+        preds, scores = [], []
+        for q in range(n):
+            ok = np.isfinite(tv[q]) & (te[q] >= 0)
+            at = np.searchsorted(ckey, q * total + te[q][ok])
+            preds.append(edges_of[at])
+            scores.append(tv[q][ok])
+        return preds, scores
+    p0 = res["path"][:, 0]
+    sign = np.where(_lowering(p0, toward, threshold), 1.0, -1.0).astype(np.float32)
+    score = np.where(cand["eligible"], sign[q_of] * (p0[q_of] - res["loo"]), -np.inf).astype(np.float32)
+    preds, scores = [], []
+    for q in range(n):
+        a, b = qp[q], qp[q + 1]
+        o = np.lexsort((cand["entry"][a:b], -score[a:b]))
+        o = o[np.isfinite(score[a:b][o])][:k]
+        preds.append(edges_of[a:b][o])
+        scores.append(score[a:b][o])
+    return preds, scores
+
+
+def counterfactual_summary(result):
+    """What a batch of searches found (host), from counterfactual_batched's dict: ``flip_rate``; ``mean_size`` and
+    ``median_size`` of the sets that flipped their prediction (0.0 when none did); ``mean_shift`` = the mean
+    |p - path[:, -1]|; ``relation_share``: the share of the removed edges per relation ({} when nothing was removed);
+    ``n``."""
+    p = np.asarray(result["p"], np.float64)
+    path = np.asarray(result["path"], np.float64)
+    flipped = np.asarray(result["flipped"], bool)
+    size = np.asarray(result["n_edges"], np.int64)
+    if path.ndim != 2 or not (len(p) == len(path) == len(flipped) == len(size) == len(result["edges"])):
+        raise ValueError("result must be counterfactual_batched's dict")
+    sets = size[flipped]
+    rels = np.concatenate([np.asarray(e, np.int64).reshape(-1, 3)[:, 1] for e in result["edges"]] +
+                          [np.zeros(0, np.int64)])
+    ids, counts = np.unique(rels, return_counts=True)
+    return dict(n=len(p), flip_rate=float(flipped.mean()) if len(p) else 0.0,
+                mean_size=float(sets.mean()) if len(sets) else 0.0,
+                median_size=float(np.median(sets)) if len(sets) else 0.0,
+                mean_shift=float(np.abs(p - path[:, -1]).mean()) if len(p) else 0.0,
+                relation_share={int(r): float(c) / len(rels) for r, c in zip(ids, counts)})
 
 
 def explanation_metrics(preds, gt, top=5, exp_num=10):

@@ -1024,6 +1024,61 @@ def explain_curves(E, K, S, Wa, ba, rel, h, r, t, qptr, crel, ccol, crole, cstep
     return deletion, insertion
 
 
+CF_MODES = {"flip": L.CF_FLIP, "lower": L.CF_LOWER, "raise": L.CF_RAISE}
+
+
+def explain_counterfactual(E, K, S, Wa, ba, rel, h, r, t, qptr, crel, ccol, crole, cpartner, celig, cval, k,
+                           toward="flip", threshold=0.5, max_cand=None, path=None, chosen=None, cstep=None,
+                           n_steps=None, flipped=None, loo=None, scratch=None):
+    """The greedy counterfactual search of Q queries and their occlusion tables (iddgcn_explain_counterfactual_f32):
+    2 max(k, 1) launches, no host read in between.  The weights, h, r, t, qptr, crel, ccol, crole and cval as in
+    explain_curves; cpartner (int32, the segment-relative index of the candidate removed together with this one, -1:
+    none) and celig (int32, 0: never removed, never evaluated): explain.counterfactual_candidates' lists (a slice of
+    qptr keeps its absolute offsets).  ``toward``: "flip", "lower" or "raise"; ``max_cand``: the longest segment
+    (sizes the grid; None: the candidate count).  Returns a dict: ``path`` (Q, k + 1) fp32, ``chosen`` (Q, k) int32,
+    ``n_steps`` and ``flipped`` (Q,) int32, ``cstep`` (int32) and ``loo`` (fp32) per candidate — allocated when not
+    given; ``scratch`` (fp32 per candidate) holds the later steps' values.  D in {32, 64}, 1 <= R <= 8,
+    0 <= k <= TOPK_MAX.  Index values are the caller's to validate (IDDGCN_CHECK_INDICES=1 checks them here)."""
+    N, D = E.shape
+    R = rel.shape[0]
+    k = int(k)
+    if not 0 <= k <= L.TOPK_MAX:
+        raise L.IddgcnError(f"explain_counterfactual: k must be in [0, {L.TOPK_MAX}]")
+    if toward not in CF_MODES:
+        raise L.IddgcnError(f"explain_counterfactual: toward must be 'flip', 'lower' or 'raise', got {toward!r}")
+    _req(E, _F32, (N, D), "E")
+    _req(rel, _F32, (R, D), "rel")
+    _req_layers(K, S, Wa, ba, R, D, "explain_counterfactual")
+    Q, C = _req_queries(h, r, t, qptr, crel, ccol, crole, N, R)
+    _req(cpartner, _I32, (C,), "cpartner")
+    _req(celig, _I32, (C,), "celig")
+    _req(cval, _F32, (C,), "cval")
+    dev = E.device
+    out = dict(path=_out(path, (Q, k + 1), _F32, dev, "path"), chosen=_out(chosen, (Q, k), _I32, dev, "chosen"),
+               cstep=_out(cstep, (C,), _I32, dev, "cstep"), n_steps=_out(n_steps, (Q,), _I32, dev, "n_steps"),
+               flipped=_out(flipped, (Q,), _I32, dev, "flipped"), loo=_out(loo, (C,), _F32, dev, "loo"))
+    scratch = _out(scratch, (C,), _F32, dev, "scratch")
+    if E.data_ptr() & 15:
+        raise L.IddgcnError("explain_counterfactual: E must be 16-byte aligned")
+    _ptr_ascends(qptr, C, "explain_counterfactual: qptr")
+    if CHECK_INDEX_RANGES and Q and C:
+        qp = qptr.cpu()
+        lens = qp[1:] - qp[:-1]
+        seg = torch.repeat_interleave(lens, lens).to(dev)                     # each candidate's segment length
+        part = cpartner[int(qp[0]):int(qp[-1])]
+        if seg.numel() != part.numel() or bool(((part < -1) | (part >= seg)).any()):
+            raise L.IddgcnError("explain_counterfactual: cpartner must lie in [-1, the segment's length)")
+    a = L.CounterfactualArgs()
+    a.N, a.d, a.R, a.k, a.Q, a.mode, a.threshold = N, D, R, k, Q, CF_MODES[toward], float(threshold)
+    a.max_cand = C if max_cand is None else int(max_cand)
+    if a.max_cand < 0:
+        raise L.IddgcnError("explain_counterfactual: max_cand must not be negative")
+    _set_ptrs(a, h=h, r=r, t=t, qptr=qptr, crel=crel, ccol=ccol, crole=crole, cpartner=cpartner, celig=celig,
+              cval=cval, E=E, rel=rel, K=K, S=S, Wa=Wa, ba=ba, scratch=scratch, **out)
+    L.check(L.lib().iddgcn_explain_counterfactual_f32(_stream(), ctypes.byref(a)), "explain_counterfactual")
+    return out
+
+
 # -- explanation ground truth (include/iddgcn_ground_truth.h) ------------------------------------
 def gt_sim_lists(sim, N):
     """Similarity lists of every node as a CSR (ptr [N+1], val [2n], first [2n]) and the device error flag (not

@@ -163,6 +163,69 @@ typedef struct {
  * or a misaligned E: IDDGCN_E_BAD_ARG. */
 int iddgcn_explain_curves_f32(void* stream, const iddgcn_explain_curves_t* args);
 
+/*
+ * Counterfactual edge sets by greedy deletion, and the occlusion table (explain.counterfactual_batched,
+ * explain.occlusion_batched).  Candidates and the forward are those of iddgcn_explain_curves_f32: for a set F of
+ * removed candidates, p(F) is its deletion forward with keep_j = [j not in F], same arithmetic and summation order, so
+ * p(F) is bitwise the last deletion point of an explanation that names exactly F.  Each candidate also carries
+ * partner_j (the segment-relative index of a candidate removed together with it, symmetric; -1: none) and elig_j
+ * (0: the candidate stays in the graph and is never evaluated).  Per query, with dir = +1 (lower p) or -1 (raise it):
+ *
+ *     mode FLIP: dir = +1 when p(0) > threshold, else -1;  LOWER: +1;  RAISE: -1
+ *     flipped(p) = !(p > threshold) when dir = +1,  p > threshold when dir = -1          (fp32 comparisons)
+ *     F = {};  path[0] = p(F);  loo[j] = p({j, partner_j}) for every eligible j, NaN for the others
+ *     for i = 0 .. K-1, while !flipped(path[i]) and an eligible candidate is left outside F:
+ *         p_j = p(F + {j, partner_j}) for every eligible j not in F
+ *         j* = the j of the smallest dir p_j; equal bit patterns: the lowest j
+ *         chosen[i] = j*;  cstep[j*] = cstep[partner_j*] = i;  F += {j*, partner_j*};  path[i + 1] = p_j*
+ *     n_steps = the steps taken;  flipped = flipped(path[n_steps]);  path past n_steps repeats path[n_steps],
+ *     chosen past it is -1, cstep of a candidate never removed is -1.
+ *
+ * The best candidate is taken even when it does not improve p.  2 max(K, 1) launches, none read by the host: a step
+ * kernel (one workgroup per (query, tile of 8 variants); variant 0 is F itself, variant 1 + j removes candidate j;
+ * a query that has stopped and a tile without an eligible remaining candidate exit at once) writes one fp32 per
+ * evaluated candidate (step 0: into loo; later steps: into scratch), a select kernel (one workgroup per query) takes
+ * the arg-min by an ordered 64-bit key and updates the outputs.  No atomics; every result of a query depends on its
+ * own candidates only: not on Q, on its place in the batch, on the other queries, on max_cand or on K (a shorter
+ * search is the prefix of a longer one).
+ */
+#define IDDGCN_CF_FLIP 0
+#define IDDGCN_CF_LOWER 1
+#define IDDGCN_CF_RAISE 2
+
+typedef struct {
+    int N, d, R;
+    int k;                           /* K: steps at most, 0 <= k <= IDDGCN_TOPK_MAX (0: only loo and path[0]) */
+    int Q;
+    int mode;                        /* IDDGCN_CF_* */
+    float threshold;
+    int max_cand;                    /* sizes the step kernel's grid: ceil((max_cand + 1) / 8) workgroups per query,
+                                        which stride over the tiles of a longer segment.  >= 0; a hint, not a bound */
+    const int* h; const int* r; const int* t;                 /* per query, int32, validated by the caller */
+    const long long* qptr;           /* (Q + 1) candidate segments */
+    const int* crel; const int* ccol; const int* crole;       /* per candidate; crel ascends in a segment */
+    const int* cpartner; const int* celig;                    /* per candidate */
+    const float* cval;               /* per candidate */
+    const float* E;                  /* (N, d), 16-byte aligned */
+    const float* K[3];               /* (R, d, d) */
+    const float* S[3];               /* (d, d) */
+    const float* Wa[3];              /* (d, R) */
+    const float* ba[3];              /* (R) */
+    const float* rel;                /* (R, d) */
+    float* path;                     /* (Q, K + 1) */
+    int* chosen;                     /* (Q, K); may be null when K == 0 */
+    int* cstep;                      /* per candidate; written, never read before it is written */
+    int* n_steps; int* flipped;      /* (Q) each */
+    float* loo;                      /* per candidate */
+    float* scratch;                  /* per candidate: the values of the steps after step 0; may be null when K <= 1 */
+} iddgcn_counterfactual_t;
+
+/* d in {32, 64} (IDDGCN_E_BAD_DIM), 1 <= R <= 8 (IDDGCN_E_BAD_REL), 0 <= k <= IDDGCN_TOPK_MAX, a mode above, Q >= 0
+ * (0: nothing launched), N >= 1, max_cand >= 0; a null pointer (the candidate arrays, cstep, loo and scratch excepted:
+ * they are never touched when every segment is empty) or a misaligned E: IDDGCN_E_BAD_ARG.  Allocates nothing and
+ * never synchronises. */
+int iddgcn_explain_counterfactual_f32(void* stream, const iddgcn_counterfactual_t* args);
+
 #ifdef __cplusplus
 }
 #endif
