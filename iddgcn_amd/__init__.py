@@ -16,6 +16,7 @@ from .metrics import classification_metrics, classification_metrics_device, rank
 from . import explain  # noqa: F401,E402  (explaiNE / GNNExplainer / IDDGCN explainer on the HIP path)
 from .explain import fidelity_curves, fidelity_summary, random_explanations  # noqa: F401,E402
 from .explain import counterfactual_batched, counterfactual_summary, occlusion_batched  # noqa: F401,E402
+from .explain import integrated_gradients_batched, integrated_gradients_summary  # noqa: F401,E402
 from . import similarity  # noqa: F401,E402  (feat_similarity.py similarity graph on MFMA)
 from . import ground_truth  # noqa: F401,E402  (explanation ground truth on the GPU, P/R/F1@k of the explainers)
 from .ground_truth import (construct_ground_truth, evaluate_explanations, filter_ground_truth,  # noqa: F401,E402

@@ -89,6 +89,19 @@ class CounterfactualArgs(ctypes.Structure):
     ]
 
 
+class ExplainPathArgs(ctypes.Structure):
+    """Mirror of iddgcn_explain_path_t (include/iddgcn_explain.h)."""
+    _fields_ = [
+        ("N", ci), ("d", ci), ("R", ci), ("Q", ci), ("m", ci),
+        ("h", vp), ("r", vp), ("t", vp), ("qptr", vp),
+        ("crel", vp), ("ccol", vp), ("crole", vp), ("celig", vp), ("cval", vp),
+        ("E", vp), ("K", vp * 3), ("KT", vp * 3), ("S", vp * 3), ("ST", vp * 3), ("Wa", vp * 3), ("ba", vp * 3),
+        ("rel", vp), ("alpha", vp), ("omega", vp),
+        ("attr", vp), ("total", vp), ("p_full", vp), ("p_base", vp), ("gap", vp), ("scratch", vp),
+    ]
+
+
+PATH_MAX_STEPS = 1024                             # include/iddgcn_explain.h IDDGCN_PATH_MAX_STEPS
 CF_FLIP, CF_LOWER, CF_RAISE = 0, 1, 2             # include/iddgcn_explain.h IDDGCN_CF_*
 TN_BATCH = 4
 SCREEN_TAIL, SCREEN_HEAD = 0, 1                   # include/iddgcn_screen.h IDDGCN_SCREEN_*
@@ -171,6 +184,9 @@ SIGNATURES = {
     "iddgcn_explain_curves_f32": (ci, [vp, ctypes.POINTER(ExplainCurvesArgs)]),
     # greedy counterfactual search and the occlusion table (added symbol only)
     "iddgcn_explain_counterfactual_f32": (ci, [vp, ctypes.POINTER(CounterfactualArgs)]),
+    # integrated gradients over the adjacency values (added symbols only)
+    "iddgcn_explain_path_scratch_floats": (cll, [ci, ci, ci, ci]),
+    "iddgcn_explain_path_f32": (ci, [vp, ctypes.POINTER(ExplainPathArgs)]),
     # include/iddgcn_ground_truth.h (explanation ground truth; added symbols only)
     "iddgcn_gt_sim_lists_workspace": (ci, [cll, ctypes.POINTER(cll)]),
     "iddgcn_gt_sim_lists": (ci, [vp, cll, ci, vp, vp, vp, vp, vp, vp, cll]),

@@ -20,7 +20,10 @@
 //
 // curves_kernel: the deletion and insertion curves of an explanation, a tile of edited forwards per workgroup.
 //
-// cf_step_kernel / cf_select_kernel (last): the greedy counterfactual search, one pair of launches per step.
+// cf_step_kernel / cf_select_kernel: the greedy counterfactual search, one pair of launches per step.
+//
+// ig_path_kernel / ig_finish_kernel (last): integrated gradients over the adjacency values, a chunk of quadrature
+// nodes per workgroup.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -1171,6 +1174,327 @@ __global__ __launch_bounds__(NT) void cf_select_kernel(const iddgcn_counterfactu
     }
 }
 
+// ---- integrated gradients over the adjacency values --------------------------------------------------------------
+// ig_path_kernel: one workgroup per (query, chunk of IG_CHUNK quadrature nodes).  The path scales the eligible
+// candidates' values by alpha, so AE(alpha) = F + alpha U and every projection is PF + alpha PU: F, U (one fmaf chain
+// per column, candidates ascending) and the 2 x 3 R projections per side are built once per workgroup, as are the
+// layer-1 terms E[h] S^1, E[t] S^1 and the layer-1 dynamic weights.  S^2, S^3 and their transposes sit in LDS, so a
+// node reads no global memory but its (alpha, omega).  Per node: the mask explainer's forward and backward (scale 1)
+// up to dz; the backward's K^T products are linear in dz, so the node loop only accumulates
+// acc[l][side][r] += omega w_lr dz^l[side] (nodes ascending) and ig_finish_kernel applies K^T once.  Chunk 0 also
+// evaluates the two end points (forward only): p_base = f(0), p_full = f(1).
+//   LDS at D = 64: S 32 KB + S^T 32 KB + PF, PU 24 KB + P 8 KB + acc 12 KB + AE 8 KB + Wa 4 KB + 3 KB = 123 KB.
+// ig_finish_kernel: one workgroup per query sums the chunks' accumulators in chunk order, applies K^T (layers
+// ascending), and gives every candidate its attribution, one candidate per thread from global memory (a row of any
+// length); total is a fixed tree over the threads' strided partial sums.
+constexpr int IG_CHUNK = 32;               // quadrature nodes per workgroup
+
+struct PathP {
+    iddgcn_explain_path_t a;
+    int nch;                               // chunks per query: ceil(m / IG_CHUNK)
+};
+
+template <int D>
+__global__ __launch_bounds__(NT) void ig_path_kernel(const PathP pp) {
+    constexpr int GR = NT / D;
+    constexpr int RPG = MAX_R / GR;
+    __shared__ float Sm[2][D * D];             // S^2, S^3
+    __shared__ float STm[2][D * D];            // their transposes
+    __shared__ float PF[3][2][MAX_R][D];
+    __shared__ float PU[3][2][MAX_R][D];
+    __shared__ float P[2][2][MAX_R][D];        // P^2, P^3 at the node's alpha (the backward's dw reads them)
+    __shared__ float acc[3][2][MAX_R][D];
+    __shared__ float AEF[2][MAX_R][D];
+    __shared__ float AEU[2][MAX_R][D];
+    __shared__ float Was[2][D * MAX_R];        // Walpha^2, Walpha^3
+    __shared__ float bas[2][MAX_R];
+    __shared__ float x[4][2][D];
+    __shared__ float c1[2][D];                 // E[h] S^1, E[t] S^1
+    __shared__ float dx[2][D];
+    __shared__ float dz[2][D];
+    __shared__ float rels[D];
+    __shared__ float w[3][MAX_R];
+    __shared__ float sm[3][MAX_R];
+    __shared__ float zs[MAX_R];
+    __shared__ float da[MAX_R];
+    __shared__ float du[MAX_R];
+    __shared__ int rstart[MAX_R + 1];
+    __shared__ float sc[1];                    // p (1 - p)
+
+    const iddgcn_explain_path_t& a = pp.a;
+    const int tid = threadIdx.x;
+    const int R = a.R;
+    const int q = blockIdx.x / pp.nch;
+    const int chunk = blockIdx.x % pp.nch;
+    const int hh = a.h[q], rr = a.r[q], tt = a.t[q];
+    const long long c0 = a.qptr[q];
+    const int n = (int)(a.qptr[q + 1] - c0);
+    const int* crel = a.crel + c0;
+    const int* ccol = a.ccol + c0;
+    const int* crole = a.crole + c0;
+    const int* celig = a.celig + c0;
+    const float* cval = a.cval + c0;
+    const int k = tid % D, grp = tid / D;
+    const int side2 = (tid / D) & 1;
+
+    // the relation segments of the candidate list, x^0, the staged matrices
+    if (tid <= MAX_R) rstart[tid] = n;
+    __syncthreads();
+    for (int j = tid; j < n; j += NT) {
+        const int r1 = crel[j];
+        const int r0 = j ? crel[j - 1] : -1;
+        for (int r = r0 + 1; r <= r1; ++r) rstart[r] = j;
+    }
+    if (tid < 2 * D) x[0][side2][k] = a.E[(size_t)(side2 ? tt : hh) * D + k];
+    if (tid < D) rels[k] = a.rel[(size_t)rr * D + k];
+    for (int idx = tid; idx < D * D; idx += NT) {
+        Sm[0][idx] = a.S[1][idx];
+        Sm[1][idx] = a.S[2][idx];
+        STm[0][idx] = a.ST[1][idx];
+        STm[1][idx] = a.ST[2][idx];
+    }
+    for (int idx = tid; idx < D * R; idx += NT) {
+        Was[0][idx] = a.Wa[1][idx];
+        Was[1][idx] = a.Wa[2][idx];
+    }
+    if (tid < R) {
+        bas[0][tid] = a.ba[1][tid];
+        bas[1][tid] = a.ba[2][tid];
+    }
+    for (int idx = tid; idx < 3 * 2 * MAX_R * D; idx += NT) (&acc[0][0][0][0])[idx] = 0.f;
+    __syncthreads();
+
+    // F and U: the fixed and the eligible part of the AE rows, candidates ascending; a candidate that does not feed a
+    // part enters it with a zero multiplier: fmaf(0, e, acc) is acc
+#pragma unroll
+    for (int ri = 0; ri < RPG; ++ri) {
+        const int r = grp + ri * GR;
+        if (r < R) {
+            float fh = 0.f, ft = 0.f, uh = 0.f, ut = 0.f;
+            const int j1 = rstart[r + 1];
+            for (int j = rstart[r]; j < j1; ++j) {
+                const float val = cval[j];
+                const int role = crole[j];
+                const bool el = celig[j] != 0;
+                const float ev = a.E[(size_t)ccol[j] * D + k];
+                const float vh = (role & 1) ? val : 0.f, vt = (role & 2) ? val : 0.f;
+                fh = fmaf(el ? 0.f : vh, ev, fh);
+                ft = fmaf(el ? 0.f : vt, ev, ft);
+                uh = fmaf(el ? vh : 0.f, ev, uh);
+                ut = fmaf(el ? vt : 0.f, ev, ut);
+            }
+            AEF[0][r][k] = fh;
+            AEF[1][r][k] = ft;
+            AEU[0][r][k] = uh;
+            AEU[1][r][k] = ut;
+        }
+    }
+    __syncthreads();
+
+    // the projections of both parts, the layer-1 logits
+    for (int l = 0; l < 3; ++l)
+        for (int r = grp; r < R; r += GR) {
+            float ph, pt;
+            matvec2<D>(a.K[l] + (size_t)r * D * D + k, AEF[0][r], AEF[1][r], ph, pt);
+            PF[l][0][r][k] = ph;
+            PF[l][1][r][k] = pt;
+            matvec2<D>(a.K[l] + (size_t)r * D * D + k, AEU[0][r], AEU[1][r], ph, pt);
+            PU[l][0][r][k] = ph;
+            PU[l][1][r][k] = pt;
+        }
+    for (int r = grp; r < R; r += GR) {
+        const float z = group_sum<D>(x[0][0][k] * a.Wa[0][(size_t)k * R + r]);
+        if (k == 0) zs[r] = z + a.ba[0][r];
+    }
+    if (tid < 2 * D) c1[side2][k] = matvec1<D>(a.S[0] + k, x[0][side2]);
+    __syncthreads();
+    if (tid < R) {
+        float mx = -INFINITY;
+        for (int i = 0; i < R; ++i) mx = fmaxf(mx, zs[i]);
+        float sum = 0.f;
+        for (int i = 0; i < R; ++i) sum += expf(zs[i] - mx);
+        const float s = expf(zs[tid] - mx) / sum;
+        sm[0][tid] = s;
+        w[0][tid] = sigmoid_ref(s);
+    }
+    __syncthreads();
+
+    const int i0 = chunk * IG_CHUNK;
+    const int cnt = a.m - i0 < IG_CHUNK ? a.m - i0 : IG_CHUNK;
+    for (int it = chunk == 0 ? -2 : 0; it < cnt; ++it) {
+        // it = -2, -1: the end points alpha = 0, 1, forward only
+        const float al = it < 0 ? (float)(it + 2) : a.alpha[i0 + it];
+        const float om = it < 0 ? 0.f : a.omega[i0 + it];
+
+        // forward; layer 1 from its constant terms
+        if (tid < 2 * D) {
+            float v = c1[side2][k];
+            for (int r = 0; r < R; ++r) v = fmaf(w[0][r], fmaf(al, PU[0][side2][r][k], PF[0][side2][r][k]), v);
+            x[1][side2][k] = sigmoid_ref(v);
+        }
+        __syncthreads();
+        for (int l = 1; l < 3; ++l) {
+            for (int r = grp; r < R; r += GR) {
+                const float z = group_sum<D>(x[l][0][k] * Was[l - 1][k * R + r]);
+                if (k == 0) zs[r] = z + bas[l - 1][r];
+            }
+            for (int idx = tid; idx < 2 * R * D; idx += NT) {
+                const int s = idx / (R * D), r = (idx / D) % R, c = idx % D;
+                P[l - 1][s][r][c] = fmaf(al, PU[l][s][r][c], PF[l][s][r][c]);
+            }
+            __syncthreads();
+            if (tid < R) {
+                float mx = -INFINITY;
+                for (int i = 0; i < R; ++i) mx = fmaxf(mx, zs[i]);
+                float sum = 0.f;
+                for (int i = 0; i < R; ++i) sum += expf(zs[i] - mx);
+                const float s = expf(zs[tid] - mx) / sum;
+                sm[l][tid] = s;
+                w[l][tid] = sigmoid_ref(s);
+            }
+            __syncthreads();
+            if (tid < 2 * D) {
+                float v = matvec1<D>(&Sm[l - 1][k], x[l][side2]);
+                for (int r = 0; r < R; ++r) v = fmaf(w[l][r], P[l - 1][side2][r][k], v);
+                x[l + 1][side2][k] = sigmoid_ref(v);
+            }
+            __syncthreads();
+        }
+        float s_dm = 0.f;
+        if (tid < D) s_dm = group_sum<D>(x[3][0][k] * rels[k] * x[3][1][k]);
+        if (tid == 0) {
+            const float p = sigmoid_ref(s_dm);
+            sc[0] = p * (1.0f - p);
+            if (it == -2) a.p_base[q] = p;
+            if (it == -1) a.p_full[q] = p;
+        }
+        __syncthreads();
+        if (it < 0) continue;                  // uniform over the workgroup
+
+        // backward up to dz of every layer
+        if (tid < 2 * D) dx[side2][k] = sc[0] * rels[k] * x[3][1 - side2][k];
+        __syncthreads();
+        for (int l = 2; l >= 0; --l) {
+            if (tid < 2 * D) {
+                const float xv = x[l + 1][side2][k];
+                dz[side2][k] = dx[side2][k] * (xv * (1.0f - xv));
+            }
+            __syncthreads();
+            for (int idx = tid; idx < 2 * R * D; idx += NT) {
+                const int s = idx / (R * D), r = (idx / D) % R, c = idx % D;
+                acc[l][s][r][c] = fmaf(om * w[l][r], dz[s][c], acc[l][s][r][c]);
+            }
+            if (l == 0) break;
+            // through the dynamic weights: dw_r = <dzh, P^l_r[h]> + <dzt, P^l_r[t]>, the sigmoid, the softmax
+            for (int r = grp; r < R; r += GR) {
+                const float dw = group_sum<D>(fmaf(dz[0][k], P[l - 1][0][r][k], dz[1][k] * P[l - 1][1][r][k]));
+                const float wv = w[l][r];
+                if (k == 0) da[r] = dw * (wv * (1.0f - wv));
+            }
+            __syncthreads();
+            if (tid < R) {
+                float sum = 0.f;
+                for (int i = 0; i < R; ++i) sum = fmaf(sm[l][i], da[i], sum);
+                du[tid] = sm[l][tid] * (da[tid] - sum);
+            }
+            __syncthreads();
+            // dx^{l-1} = dz S^l^T (+ du Walpha^l^T on the head side)
+            if (tid < 2 * D) {
+                float v = matvec1<D>(&STm[l - 1][k], dz[side2]);
+                if (side2 == 0)
+                    for (int r = 0; r < R; ++r) v = fmaf(du[r], Was[l - 1][k * R + r], v);
+                dx[side2][k] = v;
+            }
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+
+    // the chunk's accumulators, [l][side][r][column] with R relations
+    float* out = a.scratch + ((size_t)q * pp.nch + chunk) * (size_t)(6 * R * D);
+    for (int idx = tid; idx < 6 * R * D; idx += NT) {
+        const int ls = idx / (R * D), r = (idx / D) % R, c = idx % D;
+        out[idx] = acc[ls >> 1][ls & 1][r][c];
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(NT) void ig_finish_kernel(const PathP pp) {
+    constexpr int GR = NT / D;
+    __shared__ float A[3][2][MAX_R][D];
+    __shared__ __attribute__((aligned(16))) float G[2][MAX_R][D];
+    __shared__ float red[NT];
+    const iddgcn_explain_path_t& a = pp.a;
+    const int tid = threadIdx.x;
+    const int R = a.R;
+    const int q = blockIdx.x;
+    const long long c0 = a.qptr[q];
+    const int n = (int)(a.qptr[q + 1] - c0);
+    const int k = tid % D, grp = tid / D;
+
+    // the chunks in chunk order
+    const size_t sz = (size_t)(6 * R * D);
+    const float* part = a.scratch + (size_t)q * pp.nch * sz;
+    for (int idx = tid; idx < 6 * R * D; idx += NT) {
+        const int ls = idx / (R * D), r = (idx / D) % R, c = idx % D;
+        float s = part[idx];
+        for (int ch = 1; ch < pp.nch; ++ch) s += part[ch * sz + idx];
+        A[ls >> 1][ls & 1][r][c] = s;
+    }
+    __syncthreads();
+    // G_r = sum_l A^l_r K^l_r^T, layers ascending, from the transposed K
+    for (int r = grp; r < R; r += GR) {
+        float Gh = 0.f, Gt = 0.f;
+        for (int l = 0; l < 3; ++l) {
+            float gh, gt;
+            matvec2<D>(a.KT[l] + (size_t)r * D * D + k, A[l][0][r], A[l][1][r], gh, gt);
+            Gh += gh;
+            Gt += gt;
+        }
+        G[0][r][k] = Gh;
+        G[1][r][k] = Gt;
+    }
+    __syncthreads();
+
+    // per candidate: attr = val (<GH_rel, E[col]> [role & 1] + <GT_rel, E[col]> [role & 2]), exactly 0 when not eligible
+    float tot = 0.f;
+    for (int j = tid; j < n; j += NT) {
+        float at = 0.f;
+        if (a.celig[c0 + j]) {
+            const int role = a.crole[c0 + j], rl = a.crel[c0 + j];
+            const f32x4* e4 = (const f32x4*)(a.E + (size_t)a.ccol[c0 + j] * D);
+            float dot = 0.f;
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+                if (role & (1 << s)) {
+                    const f32x4* g4 = (const f32x4*)G[s][rl];
+                    f32x4 c4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int i = 0; i < D / 4; ++i) {
+                        const f32x4 ev = e4[i], gv = g4[i];
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) c4[c] = fmaf(gv[c], ev[c], c4[c]);
+                    }
+                    dot += (c4[0] + c4[1]) + (c4[2] + c4[3]);
+                }
+            at = a.cval[c0 + j] * dot;
+        }
+        a.attr[c0 + j] = at;
+        tot += at;
+    }
+    red[tid] = tot;
+    __syncthreads();
+    for (int s = NT / 2; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const float total = red[0];
+        a.total[q] = total;
+        a.gap[q] = total - (a.p_full[q] - a.p_base[q]);
+    }
+}
+
 }  // namespace xpl
 
 extern "C" {
@@ -1313,6 +1637,38 @@ int iddgcn_explain_counterfactual_f32(void* stream, const iddgcn_counterfactual_
         });
         hipLaunchKernelGGL(cf_select_kernel, dim3((unsigned)a.Q), dim3(NT), 0, st, a, i, a.k > 0 ? 1 : 0, vals);
     }
+    return (int)hipGetLastError();
+}
+
+long long iddgcn_explain_path_scratch_floats(int Q, int m, int d, int R) {
+    using namespace xpl;
+    if ((d != 32 && d != 64) || R < 1 || R > MAX_R || Q < 0 || m < 1 || m > IDDGCN_PATH_MAX_STEPS) return 0;
+    return (long long)Q * ((m + IG_CHUNK - 1) / IG_CHUNK) * 6 * R * d;
+}
+
+int iddgcn_explain_path_f32(void* stream, const iddgcn_explain_path_t* args) {
+    using namespace xpl;
+    if (!args) return IDDGCN_E_BAD_ARG;
+    const iddgcn_explain_path_t& a = *args;
+    if (a.d != 32 && a.d != 64) return IDDGCN_E_BAD_DIM;
+    if (a.R < 1 || a.R > MAX_R) return IDDGCN_E_BAD_REL;
+    if (a.m < 1 || a.m > IDDGCN_PATH_MAX_STEPS || a.Q < 0 || a.N < 1) return IDDGCN_E_BAD_ARG;
+    if (a.Q == 0) return 0;
+    if (!a.h || !a.r || !a.t || !a.qptr || !a.E || !a.rel || !a.alpha || !a.omega || !a.total || !a.p_full ||
+        !a.p_base || !a.gap || !a.scratch)
+        return IDDGCN_E_BAD_ARG;
+    // the per-candidate arrays may be null when every segment is empty: they are then never touched
+    if (!layers_ok(a.K, a.KT, a.S, a.ST, a.Wa, a.ba)) return IDDGCN_E_BAD_ARG;
+    if ((uintptr_t)a.E & 15) return IDDGCN_E_BAD_ARG;
+    PathP pp;
+    pp.a = a;
+    pp.nch = (a.m + IG_CHUNK - 1) / IG_CHUNK;
+    if ((long long)a.Q * pp.nch > 0x7fffffffLL) return IDDGCN_E_BAD_ARG;
+    const hipStream_t st = (hipStream_t)stream;
+    for_small_width(a.d, [&](auto D) {
+        hipLaunchKernelGGL(ig_path_kernel<decltype(D)::value>, dim3((unsigned)(a.Q * pp.nch)), dim3(NT), 0, st, pp);
+        hipLaunchKernelGGL(ig_finish_kernel<decltype(D)::value>, dim3((unsigned)a.Q), dim3(NT), 0, st, pp);
+    });
     return (int)hipGetLastError();
 }
 

@@ -1443,6 +1443,68 @@ class Engine:
                                            out["flipped"][q0:q1], out["loo"], scratch)
         return out
 
+    def integrated_gradients(self, params, adj, triples, cand, alpha, omega, max_entries=1 << 22):
+        """Integrated-gradients edge attributions of Q triples (ops.explain_path): per chunk two launches, every
+        quadrature node of a triple evaluated on chip.
+
+        ``cand``: explain.counterfactual_candidates' dict over ``adj`` (host arrays ``qptr``, ``rel``, ``col``,
+        ``role``, ``val``, ``eligible``); ``alpha``, ``omega``: the rule's m nodes and weights (host or device,
+        1 <= m <= 1024).  The queries run in chunks of at most ``max_entries`` candidates, at least one query each.
+        fp32 features with D in {32, 64}, 1 <= R <= 8, unsharded engine: IddgcnError otherwise
+        (explain.integrated_gradients_batched(fused=False) covers the rest).  Returns a dict of device tensors:
+        ``attr`` fp32 per candidate (exactly 0 where not eligible), ``total``, ``p_full``, ``p_base``, ``gap`` (Q,)."""
+        self.require_per_query("integrated_gradients takes D in {32, 64}, fp32 features, 1 <= R <= 8 and an unsharded "
+                               "engine: use explain.integrated_gradients_batched(fused=False) for this engine")
+        N, R, D, dev = self.N, self.R, self.D, self.device
+        if adj.num_entities != N or adj.num_relations != R:
+            raise L.IddgcnError("integrated_gradients: the adjacency is not this engine's size")
+        if int(max_entries) < 1:
+            raise ValueError(f"max_entries must be positive, got {max_entries}")
+        q = self._triples(triples, "triples", "triple")
+        Q = q.shape[0]
+        qp = np.asarray(cand["qptr"], np.int64)
+        C = len(cand["rel"])
+        if qp.shape != (Q + 1,) or qp[0] != 0 or qp[-1] != C or (np.diff(qp) < 0).any():
+            raise L.IddgcnError("integrated_gradients: cand['qptr'] must be (Q + 1,), ascending from 0 to the "
+                                "candidate count")
+        if any(len(cand[nm]) != C for nm in ("col", "role", "val", "eligible")):
+            raise L.IddgcnError("integrated_gradients: the candidate arrays must be of one length")
+        if C:
+            rel, col, role = (np.asarray(cand[nm]) for nm in ("rel", "col", "role"))
+            inner = np.ones(C, bool)
+            inner[qp[:-1][qp[:-1] < C]] = False                    # a segment's first candidate has no predecessor
+            if (rel.min() < 0 or rel.max() >= R or col.min() < 0 or col.max() >= N or role.min() < 1 or
+                    role.max() > 3 or (np.diff(rel)[inner[1:]] < 0).any()):
+                raise L.IddgcnError("integrated_gradients: candidate out of range (rel, col, role in 1..3) or "
+                                    "relations not ascending inside a query")
+        al, om = (x.to(device=dev, dtype=torch.float32).contiguous() if isinstance(x, torch.Tensor)
+                  else self.to_device(x, np.float32) for x in (alpha, omega))
+        if al.dim() != 1 or al.shape != om.shape or not 1 <= al.shape[0] <= L.PATH_MAX_STEPS:
+            raise L.IddgcnError(f"integrated_gradients: alpha and omega must be (m,) with m in [1, {L.PATH_MAX_STEPS}]")
+        g = self.to_device
+        out = dict(attr=torch.empty(C, dtype=torch.float32, device=dev),
+                   **{nm: torch.empty(Q, dtype=torch.float32, device=dev)
+                      for nm in ("total", "p_full", "p_base", "gap")})
+        if Q == 0:
+            return out
+        h, r, t, qptr = g(q[:, 0]), g(q[:, 1]), g(q[:, 2]), g(qp, np.int64)
+        crel, ccol, crole = (g(cand[nm]) for nm in ("rel", "col", "role"))
+        celig = g(np.asarray(cand["eligible"]).astype(np.int32))
+        cval = g(cand["val"], np.float32)
+        Kw, S, Wa, ba = (tuple(params[f"{nm}{l}"] for l in (1, 2, 3)) for nm in ("K", "S", "Wa", "ba"))
+        chunks = self._query_chunks(qp, max_entries)
+        need = int(L.lib().iddgcn_explain_path_scratch_floats(max(b - a for a, b in chunks), al.shape[0], D, R))
+        scratch = torch.empty(max(need, 1), dtype=torch.float32, device=dev)
+        self.finish_pending()
+        for q0, q1 in chunks:
+            with self._mark("integrated_gradients"):
+                # the chunk's own qptr slice: its offsets stay absolute, into the full candidate arrays
+                ops.explain_path(params["E"], Kw, S, Wa, ba, params["rel"], h[q0:q1], r[q0:q1], t[q0:q1],
+                                 qptr[q0:q1 + 1], crel, ccol, crole, celig, cval, al, om, out["attr"],
+                                 out["total"][q0:q1], out["p_full"][q0:q1], out["p_base"][q0:q1], out["gap"][q0:q1],
+                                 scratch)
+        return out
+
 
 def step_flops(N, R, D, T, M):
     """Algorithmic work of one training step (W_gemm)."""

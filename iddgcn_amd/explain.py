@@ -32,6 +32,9 @@ triple's explanation, every variant of a triple in one fused kernel (``fidelity_
 
 ``counterfactual_batched`` optimises what those curves measure: a greedy search for the few edges whose removal flips
 a prediction, every decision on the device; ``occlusion_batched`` ranks edges by their exact leave-one-out effect.
+
+``integrated_gradients_batched`` gives signed per-edge attributions that add up to the prediction's change against the
+graph without those edges, every quadrature node of a triple in one fused kernel (``integrated_gradients_summary``).
 """
 import contextlib
 import time
@@ -40,7 +43,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import TOPK_MAX, IddgcnError
+from ._lib import PATH_MAX_STEPS, TOPK_MAX, IddgcnError
 from .graph import DeviceAdjacency, _as_triples, get_adj_mats
 
 
@@ -1022,6 +1025,241 @@ def counterfactual_summary(result):
                 median_size=float(np.median(sets)) if len(sets) else 0.0,
                 mean_shift=float(np.abs(p - path[:, -1]).mean()) if len(p) else 0.0,
                 relation_share={int(r): float(c) / len(rels) for r, c in zip(ids, counts)})
+
+
+# -- integrated gradients: additive edge attributions ------------------------------------------------
+# How much of this prediction does each edge carry?  Signed scores that add up to p(graph) - p(baseline), the baseline
+# being the graph without the triple's eligible candidates: attr_j = val_j * integral over alpha in [0, 1] of
+# d p / d a_j along a_j = alpha val_j (include/iddgcn_explain.h has the exact rules).  Deterministic; the completeness
+# gap sum_j attr_j - (p - p_baseline) is returned with every call and measures the quadrature's error.  The bundled
+# weights saturate, so p(alpha) is close to a step: the default rule is Gauss-Legendre, which needs far fewer nodes
+# than the textbook midpoint sum there (DESIGN.md has the table).
+def quadrature_rule(steps, quadrature="gauss"):
+    """The nodes and weights (float64, (steps,) each) of a rule on [0, 1]: "gauss" (Gauss-Legendre, exact for
+    polynomials of degree 2 steps - 1) or "midpoint".  The weights sum to 1, the nodes lie inside (0, 1)."""
+    m = int(steps)
+    if not 1 <= m <= PATH_MAX_STEPS:
+        raise IddgcnError(f"steps must be in [1, {PATH_MAX_STEPS}], got {steps}")
+    if quadrature == "gauss":
+        x, w = np.polynomial.legendre.leggauss(m)
+        return 0.5 * (x + 1.0), 0.5 * w
+    if quadrature == "midpoint":
+        return (np.arange(m) + 0.5) / m, np.full(m, 1.0 / m)
+    raise IddgcnError(f"quadrature must be 'gauss' or 'midpoint', got {quadrature!r}")
+
+
+def _candidate_subset(cand, idx):
+    """The candidate dict of the queries ``idx`` (in that order) and the places of its candidates in the full arrays."""
+    qp = np.asarray(cand["qptr"], np.int64)
+    idx = np.asarray(idx, np.int64)
+    lens = qp[idx + 1] - qp[idx]
+    sub_qp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    pos = np.repeat(qp[idx] - sub_qp[:-1], lens) + np.arange(sub_qp[-1])
+    sub = {k: (np.asarray(v)[pos] if k != "qptr" else sub_qp) for k, v in cand.items()}
+    return sub, pos
+
+
+def _refine_by_gap(run, cand, n, steps, quadrature, tol, max_steps):
+    """The ``tol`` schedule: every triple with the m-node rule, then the triples whose |gap| > tol again with twice
+    the nodes, until they pass or the next rule would exceed ``max_steps``; one host read of gap per round.
+    ``run(idx, sub_cand, alpha, omega)`` returns the tensors attr / total / p_full / p_base / gap of the queries
+    ``idx``.  Returns (dict of tensors over all queries, steps_used (n,) int64, rounds)."""
+    m = int(steps)
+    idx = np.arange(n)
+    out, used, rounds = None, np.full(n, m, np.int64), 0
+    while True:
+        sub, pos = (cand, None) if out is None else _candidate_subset(cand, idx)
+        res = run(idx, sub, *quadrature_rule(m, quadrature))
+        rounds += 1
+        if out is None:
+            out = res
+        else:
+            at = torch.as_tensor(idx, device=res["gap"].device)
+            out["attr"][torch.as_tensor(pos, device=res["attr"].device)] = res["attr"]
+            for nm in ("total", "p_full", "p_base", "gap"):
+                out[nm][at] = res[nm]
+        used[idx] = m
+        if tol is None or 2 * m > int(max_steps) or not len(idx):
+            break
+        bad = np.abs(res["gap"].cpu().numpy().astype(np.float64)) > float(tol)
+        idx, m = idx[bad], 2 * m
+        if not len(idx):
+            break
+    return out, used, rounds
+
+
+def _path_layered(eng, params, dadj, triples, cand, alpha, omega):
+    """The path one node at a time on the layered kernels (any width and mode): per (triple, node) one set_values and
+    Engine.value_grads, Engine.predict for the two end points.  The fused route's cross-check; device tensors."""
+    dev = eng.device
+    base = dadj.base_values.to(torch.float32)
+    n, qp = len(triples), cand["qptr"]
+    entry = torch.as_tensor(cand["entry"].astype(np.int64), device=dev)
+    val = torch.as_tensor(cand["val"], device=dev)
+    elig = torch.as_tensor(np.asarray(cand["eligible"], bool), device=dev)
+    attr = torch.zeros(len(cand["entry"]), dtype=torch.float64, device=dev)
+    ends = torch.empty(2, n, dtype=torch.float32, device=dev)
+    for q in range(n):
+        ed = eng.edges(triples[q][None])
+        sl = slice(int(qp[q]), int(qp[q + 1]))
+        e, v, el = entry[sl], val[sl], elig[sl]
+
+        def at(a):
+            vals = base.clone()
+            vals[e] = torch.where(el, v * a, v)
+            dadj.set_values(vals)
+
+        for i, a in enumerate((0.0, 1.0)):
+            at(a)
+            ends[i, q] = eng.predict(params, dadj, ed)[0]
+        for a, w in zip(alpha, omega):
+            at(float(np.float32(a)))
+            dv, _ = eng.value_grads(params, dadj, ed)
+            attr[sl] += float(np.float32(w)) * torch.cat(dv)[e].double()
+    dadj.set_values(base)
+    attr = torch.where(elig, attr * val.double(), torch.zeros_like(attr))
+    q_of = torch.as_tensor(np.repeat(np.arange(n), np.diff(qp)), device=dev)
+    total = torch.zeros(n, dtype=torch.float64, device=dev).index_add_(0, q_of, attr)
+    gap = total - (ends[1].double() - ends[0].double())
+    return dict(attr=attr.float(), total=total.float(), p_full=ends[1], p_base=ends[0], gap=gap.float())
+
+
+def _rank_candidates(eng, dadj, cand, n, score, k):
+    """occlusion_batched's ranking of per-candidate scores (-inf: not ranked): descending, ties by ascending entry id,
+    k_q = min(k, finite scores).  A device tensor is ranked by ops.explain_topk, a host array on the host.  Returns
+    (list of (k_q, 3) int64 edge arrays, list of (k_q,) fp32 scores)."""
+    qp, edges_of = cand["qptr"], _candidate_edges(cand)
+    q_of = np.repeat(np.arange(n), np.diff(qp))
+    preds, scores = [], []
+    if isinstance(score, torch.Tensor):
+        with eng._mark("attribution_topk"):
+            te, tv, _ = ops.explain_topk(eng.to_device(qp, np.int64), eng.to_device(cand["entry"]), score, k)
+        te, tv = te.cpu().numpy().astype(np.int64), tv.cpu().numpy()
+        # entry id -> candidate: the segments ascend by entry id
+        total = dadj.total_nnz
+        ckey = q_of.astype(np.int64) * total + cand["entry"]
+        for q in range(n):
+            ok = np.isfinite(tv[q]) & (te[q] >= 0)
+            preds.append(edges_of[np.searchsorted(ckey, q * total + te[q][ok])])
+            scores.append(tv[q][ok])
+        return preds, scores
+    for q in range(n):
+        a, b = qp[q], qp[q + 1]
+        o = np.lexsort((cand["entry"][a:b], -score[a:b]))
+        o = o[np.isfinite(score[a:b][o])][:k]
+        preds.append(edges_of[a:b][o])
+        scores.append(score[a:b][o])
+    return preds, scores
+
+
+def integrated_gradients_batched(model, adjacency_data, test_triples, top_k=10, *, steps=256, quadrature="gauss",
+                                 nodes=None, tol=None, max_steps=1024, toward="flip", threshold=0.5,
+                                 exclude_target=False, relations=None, fused=None, return_attributions=False,
+                                 stats=None):
+    """Integrated-gradients edge attributions: per test triple, how much of the prediction each stored edge of rows h
+    and t carries.  The path scales the values of the triple's eligible candidates (counterfactual_candidates; the
+    others stay in the graph and get no attribution) from 0 to their stored values; attr_j = val_j * the integral of
+    d p / d a_j along it, by the rule ``quadrature`` ("gauss": Gauss-Legendre on [0, 1]; "midpoint": the textbook sum)
+    with ``steps`` nodes, or by ``nodes`` = (alpha, omega), which overrides both.  No random numbers.  Completeness:
+    the attributions of a triple add up to p - p_baseline up to ``gap``, the rule's error; with ``tol`` the triples
+    whose |gap| > tol are run again with twice the nodes until they pass or the next rule would exceed ``max_steps``
+    (one host read of gap per round).
+
+    The ranking is occlusion_batched's: the score is attr_j where the prediction is to be lowered (``toward``,
+    ``threshold``: as there, from the unedited prediction) and -attr_j where it is to be raised, eligible candidates
+    only, descending, ties by ascending entry id, ``top_k`` in 1 .. 64.  ``fused``: None takes the kernels
+    (Engine.integrated_gradients) for fp32 features, D in {32, 64}, R <= 8 and an unsharded engine; False runs one
+    set_values + Engine.value_grads per (triple, node) on the layered kernels (any width); True demands the kernels.
+    ``stats``: an optional dict that receives ``fused``, ``candidates``, ``rounds`` and, fused, ``launch_events``.
+
+    Returns a dict: ``p`` and ``p_baseline`` (n,); ``direction`` (n,) +1 where the ranking lowers p, -1 where it
+    raises it; ``edges``: a list of (k_q, 3) int64 (head, rel, tail) arrays, ready for fidelity_curves and
+    evaluate_explanations; ``scores``: a list of (k_q,) fp32; ``total`` and ``gap`` (n,); ``steps_used`` (n,);
+    ``relation_attribution`` (n, R): the attributions summed per relation (its rows sum to ``total``); with
+    ``return_attributions``, ``attributions``: a list of (candidates, 3) edge arrays and a list of their attributions
+    (NaN: not eligible), per triple."""
+    k = int(top_k)
+    if not 1 <= k <= TOPK_MAX:
+        raise IddgcnError(f"top_k must be in [1, {TOPK_MAX}], got {top_k}")
+    N, R = model.num_entities, model.num_relations
+    triples = _as_triples(test_triples)
+    if len(triples) and (triples[:, 1].min() < 0 or triples[:, 1].max() >= R):
+        raise IddgcnError("triple relation index out of range [0, num_relations)")
+    _lowering(0.0, toward, threshold)
+    if nodes is not None:
+        if tol is not None:
+            raise IddgcnError("tol doubles the rule's nodes: it cannot be combined with explicit nodes")
+        al, om = (np.asarray(x, np.float64).reshape(-1) for x in nodes)
+        if al.shape != om.shape or not 1 <= len(al) <= PATH_MAX_STEPS:
+            raise IddgcnError(f"nodes must be (alpha, omega) of one length in [1, {PATH_MAX_STEPS}]")
+    else:
+        quadrature_rule(steps, quadrature)                         # refuses a bad rule before any device work
+        if tol is not None and not int(steps) <= int(max_steps) <= PATH_MAX_STEPS:
+            raise IddgcnError(f"max_steps must lie in [steps, {PATH_MAX_STEPS}], got {max_steps}")
+    eng, params = _model_state(model)
+    fused = eng.resolve_fused(fused, eng.per_query_ok(),
+                              "integrated gradients: the fused kernels take D in {32, 64}, fp32 features, "
+                              "1 <= R <= 8 and an unsharded engine: use fused=False for this model")
+    dadj = DeviceAdjacency(get_adj_mats(adjacency_data, N, R), N, eng.device)
+    cand = counterfactual_candidates(dadj, triples, False, exclude_target, relations)
+    n = len(triples)
+
+    def run(idx, sub, alpha, omega):
+        if fused:
+            return eng.integrated_gradients(params, dadj, triples[idx], sub, alpha, omega)
+        return _path_layered(eng, params, dadj, triples[idx], sub, alpha, omega)
+
+    with _launch_events(stats) if fused else contextlib.nullcontext():
+        if nodes is not None:
+            res, used, rounds = run(np.arange(n), cand, al, om), np.full(n, len(al), np.int64), 1
+        else:
+            res, used, rounds = _refine_by_gap(run, cand, n, steps, quadrature, tol, max_steps)
+    if stats is not None:
+        stats.update(fused=bool(fused), candidates=int(len(cand["entry"])), rounds=rounds)
+    host = {nm: v.cpu().numpy() for nm, v in res.items()}
+    # the fused route ranks on the device (ops.explain_topk), the per-node route on the host
+    rank = lambda s: _rank_candidates(eng, dadj, cand, n, torch.as_tensor(s, device=eng.device) if fused else s, k)  # noqa: E731
+    return _attribution_result(cand, n, R, host, used, toward, threshold, rank, return_attributions)
+
+
+def _attribution_result(cand, n, R, host, used, toward, threshold, rank, return_attributions=False):
+    """integrated_gradients_batched's dict from the host copies of the kernel's outputs; ``rank(score)`` ranks the
+    per-candidate fp32 scores (-inf: not eligible)."""
+    qp = cand["qptr"]
+    q_of = np.repeat(np.arange(n), np.diff(qp))
+    lower = _lowering(host["p_full"], toward, threshold)
+    sign = np.where(lower, 1.0, -1.0).astype(np.float32)
+    score = np.where(cand["eligible"], sign[q_of] * host["attr"], -np.inf).astype(np.float32)
+    edges, scores = rank(score)
+    rel_attr = np.zeros((n, R), np.float64)
+    np.add.at(rel_attr, (q_of, cand["rel"].astype(np.int64)), host["attr"].astype(np.float64))
+    out = dict(p=host["p_full"], p_baseline=host["p_base"], direction=np.where(lower, 1, -1).astype(np.int64),
+               edges=edges, scores=scores, total=host["total"], gap=host["gap"], steps_used=used,
+               relation_attribution=rel_attr)
+    if return_attributions:
+        edges_of = _candidate_edges(cand)
+        table = np.where(cand["eligible"], host["attr"], np.nan).astype(np.float32)
+        out["attributions"] = ([edges_of[qp[q]:qp[q + 1]] for q in range(n)],
+                               [table[qp[q]:qp[q + 1]] for q in range(n)])
+    return out
+
+
+def integrated_gradients_summary(result, tol=1e-3):
+    """How complete a batch of attributions is (host), from integrated_gradients_batched's dict: ``mean_abs_gap`` and
+    ``max_abs_gap``; ``within_tol``: the share of triples with |gap| <= ``tol``; ``mean_shift`` = the mean
+    |p - p_baseline|; ``relation_share``: per relation, its share of sum |relation_attribution| ({} when that is 0);
+    ``mean_steps``; ``n``."""
+    gap = np.abs(np.asarray(result["gap"], np.float64))
+    p, pb = np.asarray(result["p"], np.float64), np.asarray(result["p_baseline"], np.float64)
+    ra = np.abs(np.asarray(result["relation_attribution"], np.float64))
+    if ra.ndim != 2 or not (len(gap) == len(p) == len(pb) == len(ra)):
+        raise ValueError("result must be integrated_gradients_batched's dict")
+    n, mass = len(gap), float(ra.sum())
+    return dict(n=n, mean_abs_gap=float(gap.mean()) if n else 0.0, max_abs_gap=float(gap.max()) if n else 0.0,
+                within_tol=float((gap <= tol).mean()) if n else 0.0,
+                mean_shift=float(np.abs(p - pb).mean()) if n else 0.0,
+                relation_share={int(r): float(ra[:, r].sum() / mass) for r in range(ra.shape[1])} if mass else {},
+                mean_steps=float(np.mean(result["steps_used"])) if n else 0.0)
 
 
 def explanation_metrics(preds, gt, top=5, exp_num=10):

@@ -1079,6 +1079,53 @@ def explain_counterfactual(E, K, S, Wa, ba, rel, h, r, t, qptr, crel, ccol, crol
     return out
 
 
+def explain_path(E, K, S, Wa, ba, rel, h, r, t, qptr, crel, ccol, crole, celig, cval, alpha, omega, attr=None,
+                 total=None, p_full=None, p_base=None, gap=None, scratch=None):
+    """Integrated-gradients attributions of Q queries along the path that scales their eligible candidates' values
+    from 0 to the stored ones (iddgcn_explain_path_f32), two launches.  The weights, h, r, t, qptr, crel, ccol, crole,
+    celig and cval as in explain_counterfactual (a slice of qptr keeps its absolute offsets); alpha, omega (m,) fp32:
+    the quadrature rule's nodes and weights, 1 <= m <= PATH_MAX_STEPS.  Returns a dict: ``attr`` fp32 per candidate
+    (exactly 0 where not eligible), ``total``, ``p_full``, ``p_base`` and ``gap`` = total - (p_full - p_base), (Q,)
+    fp32 each — allocated when not given; ``scratch``: fp32, at least iddgcn_explain_path_scratch_floats(Q, m, D, R)
+    long.  D in {32, 64}, 1 <= R <= 8.  Index values are the caller's to validate (IDDGCN_CHECK_INDICES=1 checks them
+    here)."""
+    N, D = E.shape
+    R = rel.shape[0]
+    _req(E, _F32, (N, D), "E")
+    _req(rel, _F32, (R, D), "rel")
+    _req_layers(K, S, Wa, ba, R, D, "explain_path")
+    Q, C = _req_queries(h, r, t, qptr, crel, ccol, crole, N, R)
+    _req(celig, _I32, (C,), "celig")
+    _req(cval, _F32, (C,), "cval")
+    _req(alpha, _F32, None, "alpha")
+    m = alpha.shape[0] if alpha.dim() == 1 else -1
+    _req(omega, _F32, (m,), "omega")
+    if not 1 <= m <= L.PATH_MAX_STEPS:
+        raise L.IddgcnError(f"explain_path: alpha and omega must be (m,) with m in [1, {L.PATH_MAX_STEPS}]")
+    dev = E.device
+    out = dict(attr=_out(attr, (C,), _F32, dev, "attr"), total=_out(total, (Q,), _F32, dev, "total"),
+               p_full=_out(p_full, (Q,), _F32, dev, "p_full"), p_base=_out(p_base, (Q,), _F32, dev, "p_base"),
+               gap=_out(gap, (Q,), _F32, dev, "gap"))
+    need = int(L.lib().iddgcn_explain_path_scratch_floats(Q, m, D, R))
+    if scratch is None:
+        scratch = torch.empty(max(need, 1), dtype=_F32, device=dev)
+    _req(scratch, _F32, None, "scratch")
+    if scratch.numel() < need:
+        raise L.IddgcnError(f"explain_path: scratch holds {scratch.numel()} floats, {need} are needed")
+    if E.data_ptr() & 15:
+        raise L.IddgcnError("explain_path: E must be 16-byte aligned")
+    _ptr_ascends(qptr, C, "explain_path: qptr")
+    a = L.ExplainPathArgs()
+    a.N, a.d, a.R, a.Q, a.m = N, D, R, Q, m
+    # the backward reads K^l_r^T and S^l^T along rows: transposed copies, made once per call
+    KT = [x.transpose(1, 2).contiguous() for x in K]
+    ST = [x.t().contiguous() for x in S]
+    _set_ptrs(a, h=h, r=r, t=t, qptr=qptr, crel=crel, ccol=ccol, crole=crole, celig=celig, cval=cval, E=E, rel=rel,
+              K=K, KT=KT, S=S, ST=ST, Wa=Wa, ba=ba, alpha=alpha, omega=omega, scratch=scratch, **out)
+    L.check(L.lib().iddgcn_explain_path_f32(_stream(), ctypes.byref(a)), "explain_path")
+    return out
+
+
 # -- explanation ground truth (include/iddgcn_ground_truth.h) ------------------------------------
 def gt_sim_lists(sim, N):
     """Similarity lists of every node as a CSR (ptr [N+1], val [2n], first [2n]) and the device error flag (not

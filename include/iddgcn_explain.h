@@ -226,6 +226,59 @@ typedef struct {
  * never synchronises. */
 int iddgcn_explain_counterfactual_f32(void* stream, const iddgcn_counterfactual_t* args);
 
+/*
+ * Integrated gradients over the adjacency values (explain.integrated_gradients_batched): signed per-edge attributions
+ * that add up to the change of the prediction between a baseline graph and the actual one.  Candidates, roles and the
+ * eligibility flag are those of iddgcn_explain_counterfactual_f32.  Along the path an eligible candidate enters with
+ * the value a_j(alpha) = val_j alpha, every other one with val_j (it stays in the graph and gets no attribution):
+ *
+ *     f(alpha)  = the mask explainer's forward with AE_r[h] = sum_{role_j & 1, rel_j = r} a_j(alpha) E[col_j], AE_r[t] alike
+ *     g_j(alpha) = d f / d a_j = <GH_rel_j, E[col_j]> [role_j & 1] + <GT_rel_j, E[col_j]> [role_j & 2]   (backward, scale 1)
+ *     attr_j = val_j sum_{i < m} omega_i g_j(alpha_i)      for the quadrature rule (alpha_i, omega_i); exactly 0 when
+ *                                                          the candidate is not eligible
+ *     p_full = f(1),  p_base = f(0),  total = sum_j attr_j,  gap = total - (p_full - p_base)
+ *
+ * For an exact integral gap is 0 (completeness); |gap| is the quadrature's error plus rounding.  AE(alpha) is linear
+ * in alpha and the backward's K^T products are linear in dz, so a node costs four d x d mat-vecs forward and four
+ * backward: a path kernel (one workgroup per (query, chunk of 32 nodes)) writes 6 R d partial sums per chunk to
+ * `scratch`, a finish kernel (one workgroup per query) adds the chunks in chunk order, applies K^T and writes the
+ * outputs.  Two launches; no atomics, no flags, no allocation, no synchronisation.  Every result of a query has a
+ * fixed summation order that depends on the query's own candidates and on the rule (m, alpha, omega) only: not on Q,
+ * the query's place in the batch or the other queries.
+ */
+#define IDDGCN_PATH_MAX_STEPS 1024
+
+typedef struct {
+    int N, d, R;
+    int Q;
+    int m;                           /* quadrature nodes, 1 <= m <= IDDGCN_PATH_MAX_STEPS */
+    const int* h; const int* r; const int* t;                 /* per query, int32, validated by the caller */
+    const long long* qptr;           /* (Q + 1) candidate segments */
+    const int* crel; const int* ccol; const int* crole;       /* per candidate; crel ascends in a segment */
+    const int* celig;                /* per candidate */
+    const float* cval;               /* per candidate */
+    const float* E;                  /* (N, d), 16-byte aligned */
+    const float* K[3];               /* (R, d, d) */
+    const float* KT[3];              /* (R, d, d): every K^l_r transposed */
+    const float* S[3];               /* (d, d) */
+    const float* ST[3];              /* (d, d): S^l transposed (ST[0] is never read) */
+    const float* Wa[3];              /* (d, R) */
+    const float* ba[3];              /* (R) */
+    const float* rel;                /* (R, d) */
+    const float* alpha; const float* omega;                   /* (m) each: the rule's nodes and weights */
+    float* attr;                     /* per candidate */
+    float* total; float* p_full; float* p_base; float* gap;   /* (Q) each */
+    float* scratch;                  /* iddgcn_explain_path_scratch_floats(Q, m, d, R) floats */
+} iddgcn_explain_path_t;
+
+/* The floats `scratch` must hold: Q * ceil(m / 32) * 6 * R * d (0 for arguments the entry below refuses). */
+long long iddgcn_explain_path_scratch_floats(int Q, int m, int d, int R);
+
+/* d in {32, 64} (IDDGCN_E_BAD_DIM), 1 <= R <= 8 (IDDGCN_E_BAD_REL), 1 <= m <= IDDGCN_PATH_MAX_STEPS, Q >= 0 (0: nothing
+ * launched), N >= 1; a null pointer (the candidate arrays and attr excepted: they are never touched when every segment
+ * is empty) or a misaligned E: IDDGCN_E_BAD_ARG. */
+int iddgcn_explain_path_f32(void* stream, const iddgcn_explain_path_t* args);
+
 #ifdef __cplusplus
 }
 #endif
