@@ -1,6 +1,7 @@
 """Helpers shared by the per-element-bound test modules (test_gpu_step_kernels.py, test_gpu_mfma_gemms.py,
 test_gpu_config5_kernels.py): the fp32 rounding unit and gamma_k, the elementwise bar with its report, NaN-guarded output
-buffers, and the interval bar of a value stored as bf16."""
+buffers, the interval bar of a value stored as bf16, and the per-query bar of the explainer gradients (query_bar:
+test_mask_grads_host.py, test_gpu_mask_grads.py)."""
 import torch
 
 F32 = torch.float32
@@ -57,6 +58,15 @@ def assert_within(got, ref, bound, what):
             f"err {float(err.flatten()[i]):.3e}, bound {float(bound.flatten()[i]):.3e}; "
             f"{int(over.sum())} of {g.numel()} elements out of bound")
     return ratio
+
+
+def query_bar(ref64, ref32, floor=1e-5):
+    """The per-query bar of the explainer gradients (tests/test_gpu_explain_batched.py's within_bar): max(4 x the
+    fp32 reference's own deviation, floor x max|ref64|), maxima over one query's values (numpy, from the reference
+    alone)."""
+    if not ref64.size:
+        return 0.0
+    return float(max(4 * abs(ref32 - ref64).max(), floor * abs(ref64).max()))
 
 
 def guarded(dev, n, *rest, fill=NAN, dtype=F32):
