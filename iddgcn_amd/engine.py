@@ -350,6 +350,51 @@ PROJ_MODES = {"exact": L.GEMM_EXACT_F32, "split": L.GEMM_SPLIT_F16, "exact4": L.
               "bf16x3": L.GEMM_BF16X3}
 
 
+def layer_tuples(params):
+    """(K, S, Wa, ba), each the three layers' tensors: how ops.mask_explain / explain_* take the weights."""
+    return tuple(tuple(params[f"{nm}{l}"] for l in (1, 2, 3)) for nm in ("K", "S", "Wa", "ba"))
+
+
+def check_candidates(who, cand, Q, N, R, extra=(), K=None):
+    """The candidate table of Q queries as Engine.edit_curves / counterfactual_search / integrated_gradients take it
+    (host arrays; DESIGN.md: the candidate table): ``qptr`` (Q + 1,) ascending from 0 to the candidate count C;
+    ``rel``, ``col``, ``role``, ``val`` and every array of ``extra`` of length C; rel in [0, R), col in [0, N), role in
+    1..3, relations ascending inside each query; of ``extra``, ``step`` lies in [-1, K) and ``partner`` in [-1, the
+    query's candidate count) and names a candidate that names it back.  IddgcnError otherwise, in ``who``'s name.
+    Returns (qptr int64, C)."""
+    if "step" in extra and K is None:
+        raise TypeError("check_candidates: 'step' is checked against K")
+    qp = np.asarray(cand["qptr"], np.int64)
+    C = len(cand["rel"])
+    if qp.shape != (Q + 1,) or qp[0] != 0 or qp[-1] != C or (np.diff(qp) < 0).any():
+        raise L.IddgcnError(f"{who}: cand['qptr'] must be (Q + 1,), ascending from 0 to the candidate count")
+    if any(len(cand[nm]) != C for nm in ("col", "role", "val", *extra)):
+        raise L.IddgcnError(f"{who}: the candidate arrays must be of one length")
+    if not C:
+        return qp, C
+    rel, col, role = (np.asarray(cand[nm]) for nm in ("rel", "col", "role"))
+    deg = np.diff(qp)
+    inner = np.ones(C, bool)
+    inner[qp[:-1][qp[:-1] < C]] = False                            # a segment's first candidate has no predecessor
+    bad = (rel.min() < 0 or rel.max() >= R or col.min() < 0 or col.max() >= N or role.min() < 1 or role.max() > 3 or
+           (np.diff(rel)[inner[1:]] < 0).any())
+    clause = ""
+    if "step" in extra:
+        step, clause = np.asarray(cand["step"]), ", step in [-1, K)"
+        bad = bad or step.min() < -1 or step.max() >= K
+    if "partner" in extra:
+        part, clause = np.asarray(cand["partner"]), ", partner in [-1, n)"
+        bad = bad or part.min() < -1 or (part >= np.repeat(deg, deg)).any()
+    if bad:
+        raise L.IddgcnError(f"{who}: candidate out of range (rel, col, role in 1..3{clause}) or relations not "
+                            "ascending inside a query")
+    if "partner" in extra:
+        first, has = np.repeat(qp[:-1], deg), part >= 0            # a partner is an index inside its own segment
+        if (part[(first + part)[has]] != (np.arange(C) - first)[has]).any():
+            raise L.IddgcnError(f"{who}: partner must be symmetric")
+    return qp, C
+
+
 class Engine:
     """Runs forward / backward / Adam for one (graph, scored-edge batch).
 
@@ -609,6 +654,31 @@ class Engine:
         if len(q) and (q[:, 1].min() < 0 or q[:, 1].max() >= self.R):
             raise L.IddgcnError(f"{one} relation index out of range [0, num_relations)")
         return q
+
+    def _candidate_checks(self, who, envelope, adj, triples, cand, max_entries, extra=(), K=None):
+        """The refusals of a method over a candidate table, before anything is allocated or uploaded: ``envelope`` (the
+        message outside the per-query kernels' envelope), the adjacency's size, max_entries, the triples,
+        check_candidates.  Returns (triples int64 (Q, 3), qptr int64, C)."""
+        self.require_per_query(envelope)
+        if adj.num_entities != self.N or adj.num_relations != self.R:
+            raise L.IddgcnError(f"{who}: the adjacency is not this engine's size")
+        if int(max_entries) < 1:
+            raise ValueError(f"max_entries must be positive, got {max_entries}")
+        q = self._triples(triples, "triples", "triple")
+        return (q, *check_candidates(who, cand, q.shape[0], self.N, self.R, extra, K))
+
+    def _candidate_uploads(self, params, q, qp, cand, max_entries, extra=()):
+        """The checked table on the device, once per call (Q > 0).  Returns (queries, c, layers, chunks): ``c`` the
+        candidate arrays by name (``val`` fp32, the others and every array of ``extra`` int32; ``eligible`` 0 / 1),
+        ``chunks`` the query ranges of at most ``max_entries`` candidates, at least one query each, and
+        ``queries(q0, q1)`` the (h, r, t, qptr) of one.  The chunk's own qptr slice: its offsets stay absolute, into
+        the full candidate arrays."""
+        g = self.to_device
+        h, r, t, qptr = g(q[:, 0]), g(q[:, 1]), g(q[:, 2]), g(qp, np.int64)
+        c = {nm: g(cand[nm]) for nm in ("rel", "col", "role", *extra)}
+        c["val"] = g(cand["val"], np.float32)
+        queries = lambda q0, q1: (h[q0:q1], r[q0:q1], t[q0:q1], qptr[q0:q1 + 1])  # noqa: E731
+        return queries, c, layer_tuples(params), self._query_chunks(qp, max_entries)
 
     def _ae(self, adj, E, ws, r=None, n0=0, n1=0):
         """AE_r = A_r·E (IDDGCN.py:69-70): all relations in one launch, or the rows [n0, n1) of relation r."""
@@ -1330,47 +1400,23 @@ class Engine:
         least one query each.  fp32 features with D in {32, 64}, 1 <= R <= 8, unsharded engine: IddgcnError otherwise
         (explain.fidelity_curves(fused=False) covers the rest).  Returns (deletion, insertion): (Q, K + 1) fp32
         device tensors."""
-        self.require_per_query("edit_curves takes D in {32, 64}, fp32 features, 1 <= R <= 8 and an unsharded engine: "
-                               "use explain.fidelity_curves(fused=False) for this engine")
-        N, R, dev = self.N, self.R, self.device
         K = int(K)
         if not 1 <= K <= L.TOPK_MAX:
             raise L.IddgcnError(f"edit_curves: K must be in [1, {L.TOPK_MAX}], got {K}")
-        if adj.num_entities != N or adj.num_relations != R:
-            raise L.IddgcnError("edit_curves: the adjacency is not this engine's size")
-        if int(max_entries) < 1:
-            raise ValueError(f"max_entries must be positive, got {max_entries}")
-        q = self._triples(triples, "triples", "triple")
+        q, qp, _ = self._candidate_checks("edit_curves", "edit_curves takes D in {32, 64}, fp32 features, 1 <= R <= 8 "
+                                          "and an unsharded engine: use explain.fidelity_curves(fused=False) for this "
+                                          "engine", adj, triples, cand, max_entries, ("step",), K)
         Q = q.shape[0]
-        qp = np.asarray(cand["qptr"], np.int64)
-        C = len(cand["rel"])
-        if qp.shape != (Q + 1,) or qp[0] != 0 or qp[-1] != C or (np.diff(qp) < 0).any():
-            raise L.IddgcnError("edit_curves: cand['qptr'] must be (Q + 1,), ascending from 0 to the candidate count")
-        if any(len(cand[nm]) != C for nm in ("col", "role", "step", "val")):
-            raise L.IddgcnError("edit_curves: the candidate arrays must be of one length")
-        if C:
-            rel, col, role, step = (np.asarray(cand[nm]) for nm in ("rel", "col", "role", "step"))
-            inner = np.ones(C, bool)
-            inner[qp[:-1][qp[:-1] < C]] = False                    # a segment's first candidate has no predecessor
-            if (rel.min() < 0 or rel.max() >= R or col.min() < 0 or col.max() >= N or role.min() < 1 or
-                    role.max() > 3 or step.min() < -1 or step.max() >= K or (np.diff(rel)[inner[1:]] < 0).any()):
-                raise L.IddgcnError("edit_curves: candidate out of range (rel, col, role in 1..3, step in [-1, K)) "
-                                    "or relations not ascending inside a query")
-        g = self.to_device
-        dele = torch.empty(Q, K + 1, dtype=torch.float32, device=dev)
-        ins = torch.empty(Q, K + 1, dtype=torch.float32, device=dev)
+        dele = torch.empty(Q, K + 1, dtype=torch.float32, device=self.device)
+        ins = torch.empty(Q, K + 1, dtype=torch.float32, device=self.device)
         if Q == 0:
             return dele, ins
-        h, r, t, qptr = g(q[:, 0]), g(q[:, 1]), g(q[:, 2]), g(qp, np.int64)
-        crel, ccol, crole, cstep = (g(cand[nm]) for nm in ("rel", "col", "role", "step"))
-        cval = g(cand["val"], np.float32)
-        Kw, S, Wa, ba = (tuple(params[f"{nm}{l}"] for l in (1, 2, 3)) for nm in ("K", "S", "Wa", "ba"))
+        queries, c, layers, chunks = self._candidate_uploads(params, q, qp, cand, max_entries, ("step",))
         self.finish_pending()
-        for q0, q1 in self._query_chunks(qp, max_entries):
+        for q0, q1 in chunks:
             with self._mark("edit_curves"):
-                # the chunk's own qptr slice: its offsets stay absolute, into the full candidate arrays
-                ops.explain_curves(params["E"], Kw, S, Wa, ba, params["rel"], h[q0:q1], r[q0:q1], t[q0:q1],
-                                   qptr[q0:q1 + 1], crel, ccol, crole, cstep, cval, K, dele[q0:q1], ins[q0:q1])
+                ops.explain_curves(params["E"], *layers, params["rel"], *queries(q0, q1), c["rel"], c["col"],
+                                   c["role"], c["step"], c["val"], K, dele[q0:q1], ins[q0:q1])
         return dele, ins
 
     def counterfactual_search(self, params, adj, triples, cand, K, toward="flip", threshold=0.5,
@@ -1384,40 +1430,15 @@ class Engine:
         {32, 64}, 1 <= R <= 8, unsharded engine: IddgcnError otherwise (explain.counterfactual_batched(fused=False)
         covers the rest).  Returns a dict of device tensors: ``path`` (Q, K + 1), ``chosen`` (Q, K) int32, ``n_steps``,
         ``flipped`` (Q,) int32, ``cstep`` int32 and ``loo`` fp32 per candidate."""
-        self.require_per_query("counterfactual_search takes D in {32, 64}, fp32 features, 1 <= R <= 8 and an "
-                               "unsharded engine: use explain.counterfactual_batched(fused=False) for this engine")
-        N, R, dev = self.N, self.R, self.device
         K = int(K)
         if not 0 <= K <= L.TOPK_MAX:
             raise L.IddgcnError(f"counterfactual_search: K must be in [0, {L.TOPK_MAX}], got {K}")
-        if adj.num_entities != N or adj.num_relations != R:
-            raise L.IddgcnError("counterfactual_search: the adjacency is not this engine's size")
-        if int(max_entries) < 1:
-            raise ValueError(f"max_entries must be positive, got {max_entries}")
-        q = self._triples(triples, "triples", "triple")
-        Q = q.shape[0]
-        qp = np.asarray(cand["qptr"], np.int64)
-        C = len(cand["rel"])
-        if qp.shape != (Q + 1,) or qp[0] != 0 or qp[-1] != C or (np.diff(qp) < 0).any():
-            raise L.IddgcnError("counterfactual_search: cand['qptr'] must be (Q + 1,), ascending from 0 to the "
-                                "candidate count")
-        if any(len(cand[nm]) != C for nm in ("col", "role", "val", "partner", "eligible")):
-            raise L.IddgcnError("counterfactual_search: the candidate arrays must be of one length")
-        deg = np.diff(qp)
-        if C:
-            rel, col, role, part = (np.asarray(cand[nm]) for nm in ("rel", "col", "role", "partner"))
-            inner = np.ones(C, bool)
-            inner[qp[:-1][qp[:-1] < C]] = False                    # a segment's first candidate has no predecessor
-            has = part >= 0
-            at = np.repeat(qp[:-1], deg) + np.where(has, part, 0)  # the partner's absolute place
-            if (rel.min() < 0 or rel.max() >= R or col.min() < 0 or col.max() >= N or role.min() < 1 or
-                    role.max() > 3 or part.min() < -1 or (part >= np.repeat(deg, deg)).any() or
-                    (np.diff(rel)[inner[1:]] < 0).any()):
-                raise L.IddgcnError("counterfactual_search: candidate out of range (rel, col, role in 1..3, partner "
-                                    "in [-1, n)) or relations not ascending inside a query")
-            if (part[at[has]] != (np.arange(C) - np.repeat(qp[:-1], deg))[has]).any():
-                raise L.IddgcnError("counterfactual_search: partner must be symmetric")
-        g = self.to_device
+        extra = ("partner", "eligible")
+        q, qp, C = self._candidate_checks("counterfactual_search", "counterfactual_search takes D in {32, 64}, fp32 "
+                                          "features, 1 <= R <= 8 and an unsharded engine: use "
+                                          "explain.counterfactual_batched(fused=False) for this engine",
+                                          adj, triples, cand, max_entries, extra)
+        Q, dev = q.shape[0], self.device
         out = dict(path=torch.empty(Q, K + 1, dtype=torch.float32, device=dev),
                    chosen=torch.empty(Q, K, dtype=torch.int32, device=dev),
                    n_steps=torch.empty(Q, dtype=torch.int32, device=dev),
@@ -1427,17 +1448,13 @@ class Engine:
         if Q == 0:
             return out
         scratch = torch.empty(C, dtype=torch.float32, device=dev)
-        h, r, t, qptr = g(q[:, 0]), g(q[:, 1]), g(q[:, 2]), g(qp, np.int64)
-        crel, ccol, crole, cpart = (g(cand[nm]) for nm in ("rel", "col", "role", "partner"))
-        celig = g(np.asarray(cand["eligible"]).astype(np.int32))
-        cval = g(cand["val"], np.float32)
-        Kw, S, Wa, ba = (tuple(params[f"{nm}{l}"] for l in (1, 2, 3)) for nm in ("K", "S", "Wa", "ba"))
+        queries, c, layers, chunks = self._candidate_uploads(params, q, qp, cand, max_entries, extra)
+        deg = np.diff(qp)
         self.finish_pending()
-        for q0, q1 in self._query_chunks(qp, max_entries):
+        for q0, q1 in chunks:
             with self._mark("counterfactual_search"):
-                # the chunk's own qptr slice: its offsets stay absolute, into the full candidate arrays
-                ops.explain_counterfactual(params["E"], Kw, S, Wa, ba, params["rel"], h[q0:q1], r[q0:q1], t[q0:q1],
-                                           qptr[q0:q1 + 1], crel, ccol, crole, cpart, celig, cval, K, toward,
+                ops.explain_counterfactual(params["E"], *layers, params["rel"], *queries(q0, q1), c["rel"],
+                                           c["col"], c["role"], c["partner"], c["eligible"], c["val"], K, toward,
                                            threshold, int(deg[q0:q1].max()), out["path"][q0:q1],
                                            out["chosen"][q0:q1], out["cstep"], out["n_steps"][q0:q1],
                                            out["flipped"][q0:q1], out["loo"], scratch)
@@ -1453,56 +1470,30 @@ class Engine:
         fp32 features with D in {32, 64}, 1 <= R <= 8, unsharded engine: IddgcnError otherwise
         (explain.integrated_gradients_batched(fused=False) covers the rest).  Returns a dict of device tensors:
         ``attr`` fp32 per candidate (exactly 0 where not eligible), ``total``, ``p_full``, ``p_base``, ``gap`` (Q,)."""
-        self.require_per_query("integrated_gradients takes D in {32, 64}, fp32 features, 1 <= R <= 8 and an unsharded "
-                               "engine: use explain.integrated_gradients_batched(fused=False) for this engine")
-        N, R, D, dev = self.N, self.R, self.D, self.device
-        if adj.num_entities != N or adj.num_relations != R:
-            raise L.IddgcnError("integrated_gradients: the adjacency is not this engine's size")
-        if int(max_entries) < 1:
-            raise ValueError(f"max_entries must be positive, got {max_entries}")
-        q = self._triples(triples, "triples", "triple")
-        Q = q.shape[0]
-        qp = np.asarray(cand["qptr"], np.int64)
-        C = len(cand["rel"])
-        if qp.shape != (Q + 1,) or qp[0] != 0 or qp[-1] != C or (np.diff(qp) < 0).any():
-            raise L.IddgcnError("integrated_gradients: cand['qptr'] must be (Q + 1,), ascending from 0 to the "
-                                "candidate count")
-        if any(len(cand[nm]) != C for nm in ("col", "role", "val", "eligible")):
-            raise L.IddgcnError("integrated_gradients: the candidate arrays must be of one length")
-        if C:
-            rel, col, role = (np.asarray(cand[nm]) for nm in ("rel", "col", "role"))
-            inner = np.ones(C, bool)
-            inner[qp[:-1][qp[:-1] < C]] = False                    # a segment's first candidate has no predecessor
-            if (rel.min() < 0 or rel.max() >= R or col.min() < 0 or col.max() >= N or role.min() < 1 or
-                    role.max() > 3 or (np.diff(rel)[inner[1:]] < 0).any()):
-                raise L.IddgcnError("integrated_gradients: candidate out of range (rel, col, role in 1..3) or "
-                                    "relations not ascending inside a query")
+        q, qp, C = self._candidate_checks("integrated_gradients", "integrated_gradients takes D in {32, 64}, fp32 "
+                                          "features, 1 <= R <= 8 and an unsharded engine: use "
+                                          "explain.integrated_gradients_batched(fused=False) for this engine",
+                                          adj, triples, cand, max_entries, ("eligible",))
+        Q, dev = q.shape[0], self.device
         al, om = (x.to(device=dev, dtype=torch.float32).contiguous() if isinstance(x, torch.Tensor)
                   else self.to_device(x, np.float32) for x in (alpha, omega))
         if al.dim() != 1 or al.shape != om.shape or not 1 <= al.shape[0] <= L.PATH_MAX_STEPS:
             raise L.IddgcnError(f"integrated_gradients: alpha and omega must be (m,) with m in [1, {L.PATH_MAX_STEPS}]")
-        g = self.to_device
         out = dict(attr=torch.empty(C, dtype=torch.float32, device=dev),
                    **{nm: torch.empty(Q, dtype=torch.float32, device=dev)
                       for nm in ("total", "p_full", "p_base", "gap")})
         if Q == 0:
             return out
-        h, r, t, qptr = g(q[:, 0]), g(q[:, 1]), g(q[:, 2]), g(qp, np.int64)
-        crel, ccol, crole = (g(cand[nm]) for nm in ("rel", "col", "role"))
-        celig = g(np.asarray(cand["eligible"]).astype(np.int32))
-        cval = g(cand["val"], np.float32)
-        Kw, S, Wa, ba = (tuple(params[f"{nm}{l}"] for l in (1, 2, 3)) for nm in ("K", "S", "Wa", "ba"))
-        chunks = self._query_chunks(qp, max_entries)
-        need = int(L.lib().iddgcn_explain_path_scratch_floats(max(b - a for a, b in chunks), al.shape[0], D, R))
+        queries, c, layers, chunks = self._candidate_uploads(params, q, qp, cand, max_entries, ("eligible",))
+        need = int(L.lib().iddgcn_explain_path_scratch_floats(max(q1 - q0 for q0, q1 in chunks), al.shape[0],
+                                                              self.D, self.R))
         scratch = torch.empty(max(need, 1), dtype=torch.float32, device=dev)
         self.finish_pending()
         for q0, q1 in chunks:
             with self._mark("integrated_gradients"):
-                # the chunk's own qptr slice: its offsets stay absolute, into the full candidate arrays
-                ops.explain_path(params["E"], Kw, S, Wa, ba, params["rel"], h[q0:q1], r[q0:q1], t[q0:q1],
-                                 qptr[q0:q1 + 1], crel, ccol, crole, celig, cval, al, om, out["attr"],
-                                 out["total"][q0:q1], out["p_full"][q0:q1], out["p_base"][q0:q1], out["gap"][q0:q1],
-                                 scratch)
+                ops.explain_path(params["E"], *layers, params["rel"], *queries(q0, q1), c["rel"], c["col"],
+                                 c["role"], c["eligible"], c["val"], al, om, out["attr"], out["total"][q0:q1],
+                                 out["p_full"][q0:q1], out["p_base"][q0:q1], out["gap"][q0:q1], scratch)
         return out
 
 

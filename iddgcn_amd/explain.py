@@ -44,6 +44,7 @@ import torch
 
 from . import ops
 from ._lib import PATH_MAX_STEPS, TOPK_MAX, IddgcnError
+from .engine import layer_tuples
 from .graph import DeviceAdjacency, _as_triples, get_adj_mats
 
 
@@ -405,6 +406,51 @@ def _launch_events(stats):
     stats.update(launch_events=ev)
 
 
+def _checked_triples(test_triples, R):
+    """(n, 3) int64 triples whose relations lie in [0, R)."""
+    triples = _as_triples(test_triples)
+    if len(triples) and (triples[:, 1].min() < 0 or triples[:, 1].max() >= R):
+        raise IddgcnError("triple relation index out of range [0, num_relations)")
+    return triples
+
+
+def _fused_or_layered(model, adjacency_data, test_triples, fused, message):
+    """How an explainer with a fused per-query route and a layered one opens: (eng, params, checked triples, the
+    resolved ``fused`` — IddgcnError ``message`` when the kernels are demanded outside their envelope —, the device
+    adjacency of ``adjacency_data``)."""
+    N, R = model.num_entities, model.num_relations
+    triples = _checked_triples(test_triples, R)                    # refused before any device work
+    eng, params = _model_state(model)
+    fused = eng.resolve_fused(fused, eng.per_query_ok(), message)
+    return eng, params, triples, fused, DeviceAdjacency(get_adj_mats(adjacency_data, N, R), N, eng.device)
+
+
+def _note_route(stats, fused, cand, **more):
+    """The ``stats`` every such explainer leaves: the route taken and the candidate count."""
+    if stats is not None:
+        stats.update(fused=bool(fused), candidates=int(len(cand["entry"])), **more)
+
+
+class _EditedAdjacency:
+    """The layered routes' scaffolding: ``base``, the stored values in fp32, of which every variant is an edited clone
+    handed to ``dadj.set_values``; ``entry``, the candidates' entry ids on the device; ``edges(q)``, triple q as the
+    ScoredEdges Engine.predict / value_grads take; and the stored values back in ``dadj`` on the way out."""
+
+    def __init__(self, eng, dadj, triples, cand):
+        self.eng, self.dadj, self.triples = eng, dadj, triples
+        self.base = dadj.base_values.to(torch.float32)
+        self.entry = torch.as_tensor(cand["entry"].astype(np.int64), device=eng.device)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.dadj.set_values(self.base)
+
+    def edges(self, q):
+        return self.eng.edges(self.triples[q][None])
+
+
 def mask_candidates(dadj, triples):
     """The computation graphs of Q triples as candidate lists over the full adjacency ``dadj`` (a DeviceAdjacency of
     get_adj_mats(adjacency_data), host entry order: relation-major, row-major sorted).  A triple's candidates are the
@@ -503,10 +549,8 @@ def mask_explainer_batched(model, adjacency_data, test_triples, *, num_epochs=5,
                           "engine: use the per-triple mask_explainer for this model")
     if target_ratios is not None and len(target_ratios) != R:
         raise IddgcnError("target_ratios needs one entry per relation")
-    triples = _as_triples(test_triples)
+    triples = _checked_triples(test_triples, R)
     Q = len(triples)
-    if Q and (triples[:, 1].min() < 0 or triples[:, 1].max() >= R):
-        raise IddgcnError("triple relation index out of range [0, num_relations)")
     if init_value is None:
         init_value = np.random.default_rng(seed).standard_normal((N, N)).astype(np.float32)
     init = np.asarray(init_value, np.float32).reshape(N, N)
@@ -539,10 +583,9 @@ def mask_explainer_batched(model, adjacency_data, test_triples, *, num_epochs=5,
     out = torch.empty(len(entry), dtype=torch.float32, device=dev)
     d_qptr, d_entry = g(qptr, np.int64), g(entry)
     if Q:
-        K, S, Wa, ba = (tuple(params[f"{nm}{l}"] for l in (1, 2, 3)) for nm in ("K", "S", "Wa", "ba"))
         eng.finish_pending()
         with _launch_events(stats), eng._mark("mask_explain"):
-            ops.mask_explain(params["E"], K, S, Wa, ba, params["rel"], g(triples[:, 0]), g(triples[:, 1]),
+            ops.mask_explain(params["E"], *layer_tuples(params), params["rel"], g(triples[:, 0]), g(triples[:, 1]),
                              g(triples[:, 2]), d_qptr, d_entry, g(crel), g(ccol), g(crole),
                              g(init[row, col], np.float32), m, v, steps, alpha, out, g(order), level_ptr, num_epochs,
                              0, b1, b2, eps, None if target_ratios is None else g(target_ratios, np.float32))
@@ -628,14 +671,18 @@ def _padded_explanations(preds, n):
 
 
 def _row_candidates(dadj, triples):
-    """mask_candidates restricted to role != 0 (the entry's row is h or t) and each candidate's stored value."""
+    """mask_candidates restricted to role != 0 (the entry's row is h or t) and each candidate's stored value, as the
+    candidate table's common part — ``qptr`` (n + 1,) int64; ``entry``, ``rel``, ``col``, ``role`` int32; ``val`` fp32 —
+    and the query of every candidate (int64)."""
     qptr, entry, crel, ccol, crole = mask_candidates(dadj, triples)
     keep = crole != 0
     q_of = np.repeat(np.arange(len(qptr) - 1), np.diff(qptr))[keep]
     qptr = np.concatenate([[0], np.cumsum(np.bincount(q_of, minlength=len(qptr) - 1))]).astype(np.int64)
     entry = entry[keep]
     val = dadj.base_values.cpu().numpy().astype(np.float32)[entry]
-    return qptr, q_of, entry, crel[keep], ccol[keep], crole[keep], val
+    i32 = lambda a: a.astype(np.int32, copy=False)  # noqa: E731
+    return dict(qptr=qptr, entry=i32(entry), rel=i32(crel[keep]), col=i32(ccol[keep]), role=i32(crole[keep]),
+                val=val), q_of
 
 
 def curve_steps(dadj, triples, preds, undirected=False):
@@ -652,7 +699,8 @@ def curve_steps(dadj, triples, preds, undirected=False):
     n, N, total = len(tr), dadj.num_entities, dadj.total_nnz
     ex = _padded_explanations(preds, n)
     K = ex.shape[1]
-    qptr, q_of, entry, crel, ccol, crole, val = _row_candidates(dadj, tr)
+    cand, q_of = _row_candidates(dadj, tr)
+    entry = cand["entry"]
     # stored (rel, row, col) -> entry id, through one sorted 64-bit key
     row, col, rel, real = _entry_table(dadj)
     ids = np.flatnonzero(real)
@@ -676,34 +724,30 @@ def curve_steps(dadj, triples, preds, undirected=False):
     step[step == K] = -1
     effective = np.zeros((n, K), bool)
     effective[q_of[step >= 0], step[step >= 0]] = True
-    i32 = np.int32
-    return dict(qptr=qptr, entry=entry.astype(i32), rel=crel.astype(i32), col=ccol.astype(i32),
-                role=crole.astype(i32), step=step.astype(i32), val=val, effective=effective, K=K)
+    return dict(cand, step=step.astype(np.int32), effective=effective, K=K)
 
 
 def _curves_layered(eng, params, dadj, triples, cand, K):
     """One set_values + Engine.predict per variant (any width and mode): the route a user had before the fused kernel,
     its cross-check and its timing baseline."""
     dev = eng.device
-    base = dadj.base_values.to(torch.float32)
     n = len(triples)
     out = torch.empty(2, n, K + 1, dtype=torch.float32, device=dev)
     qp = cand["qptr"]
-    entry = torch.as_tensor(cand["entry"].astype(np.int64), device=dev)
     step = torch.as_tensor(cand["step"].astype(np.int64), device=dev)
     val = torch.as_tensor(cand["val"], device=dev)
-    for q in range(n):
-        ed = eng.edges(triples[q][None])
-        e, st, v = (x[qp[q]:qp[q + 1]] for x in (entry, step, val))
-        zero = torch.zeros_like(v)
-        for j in range(K + 1):
-            flipped = (st >= 0) & (st < j)
-            for which, keep in ((0, ~flipped), (1, flipped)):
-                vals = base.clone()
-                vals[e] = torch.where(keep, v, zero)
-                dadj.set_values(vals)
-                out[which, q, j] = eng.predict(params, dadj, ed)[0]
-    dadj.set_values(base)
+    with _EditedAdjacency(eng, dadj, triples, cand) as adj:
+        for q in range(n):
+            ed = adj.edges(q)
+            e, st, v = (x[qp[q]:qp[q + 1]] for x in (adj.entry, step, val))
+            zero = torch.zeros_like(v)
+            for j in range(K + 1):
+                flipped = (st >= 0) & (st < j)
+                for which, keep in ((0, ~flipped), (1, flipped)):
+                    vals = adj.base.clone()
+                    vals[e] = torch.where(keep, v, zero)
+                    dadj.set_values(vals)
+                    out[which, q, j] = eng.predict(params, dadj, ed)[0]
     return out[0], out[1]
 
 
@@ -722,15 +766,10 @@ def fidelity_curves(model, adjacency_data, test_triples, preds, *, undirected=Fa
     ``candidates`` and, on the fused route, ``launch_events`` (a pair of recorded device events around the launches).
     Returns a dict of numpy arrays: ``p`` (n,), ``deletion`` (n, K + 1), ``insertion`` (n, K + 1), ``effective``
     (n, K) bool."""
-    eng, params = _model_state(model)
-    N, R = model.num_entities, model.num_relations
-    triples = _as_triples(test_triples)
-    if len(triples) and (triples[:, 1].min() < 0 or triples[:, 1].max() >= R):
-        raise IddgcnError("triple relation index out of range [0, num_relations)")
-    fused = eng.resolve_fused(fused, eng.per_query_ok(),
-                              "fidelity_curves: the fused kernel takes D in {32, 64}, fp32 features, 1 <= R <= 8 and "
-                              "an unsharded engine: use fused=False for this model")
-    dadj = DeviceAdjacency(get_adj_mats(adjacency_data, N, R), N, eng.device)
+    eng, params, triples, fused, dadj = _fused_or_layered(
+        model, adjacency_data, test_triples, fused,
+        "fidelity_curves: the fused kernel takes D in {32, 64}, fp32 features, 1 <= R <= 8 and an unsharded engine: "
+        "use fused=False for this model")
     cand = curve_steps(dadj, triples, preds, undirected)
     K = cand["K"]
     if fused:
@@ -738,8 +777,7 @@ def fidelity_curves(model, adjacency_data, test_triples, preds, *, undirected=Fa
             dele, ins = eng.edit_curves(params, dadj, triples, cand, K)
     else:
         dele, ins = _curves_layered(eng, params, dadj, triples, cand, K)
-    if stats is not None:
-        stats.update(fused=bool(fused), candidates=int(len(cand["entry"])))
+    _note_route(stats, fused, cand)
     dele, ins = dele.cpu().numpy(), ins.cpu().numpy()
     return dict(p=dele[:, 0].copy(), deletion=dele, insertion=ins, effective=cand["effective"])
 
@@ -773,11 +811,12 @@ def random_explanations(dadj, triples, k, seed=0):
     k = int(k)
     if k < 1:
         raise ValueError(f"k must be positive, got {k}")
-    qptr, q_of, entry, crel, ccol, _, _ = _row_candidates(dadj, tr)
+    cand, q_of = _row_candidates(dadj, tr)
+    qptr, entry = cand["qptr"], cand["entry"]
     row = _entry_table(dadj, real=False)[0]
     draw = np.random.default_rng(seed).random(len(entry))
     order = np.lexsort((draw, q_of))                                # a random order inside every triple's segment
-    edges = np.stack([row[entry], crel.astype(np.int64), ccol.astype(np.int64)], 1)[order]
+    edges = np.stack([row[entry], cand["rel"].astype(np.int64), cand["col"].astype(np.int64)], 1)[order]
     return [edges[qptr[q]:min(qptr[q] + k, qptr[q + 1])] for q in range(len(tr))]
 
 
@@ -798,9 +837,10 @@ def counterfactual_candidates(dadj, triples, undirected=False, exclude_target=Fa
     ``col``, ``role``, ``row``, ``partner`` (int32), ``val`` (fp32) and ``eligible`` (bool)."""
     tr = _as_triples(triples)
     n, N, R = len(tr), dadj.num_entities, dadj.num_relations
-    qptr, q_of, entry, crel, ccol, crole, val = _row_candidates(dadj, tr)
-    crow = _entry_table(dadj, real=False)[0][entry]
-    C = len(entry)
+    cand, q_of = _row_candidates(dadj, tr)
+    qptr, crel, ccol = cand["qptr"], cand["rel"], cand["col"]
+    crow = _entry_table(dadj, real=False)[0][cand["entry"]]
+    C = len(crow)
     within = np.arange(C) - qptr[:-1][q_of]
     partner = np.full(C, -1, np.int64)
     if undirected and C:
@@ -819,10 +859,7 @@ def counterfactual_candidates(dadj, triples, undirected=False, exclude_target=Fa
         if len(rels) and (rels.min() < 0 or rels.max() >= R):
             raise IddgcnError("relations: index out of range [0, num_relations)")
         eligible &= np.isin(crel, rels)
-    i32 = np.int32
-    return dict(qptr=qptr, entry=entry.astype(i32), rel=crel.astype(i32), col=ccol.astype(i32),
-                role=crole.astype(i32), row=crow.astype(i32), partner=partner.astype(i32), val=val,
-                eligible=eligible)
+    return dict(cand, row=crow.astype(np.int32), partner=partner.astype(np.int32), eligible=eligible)
 
 
 def _lowering(p0, toward, threshold):
@@ -839,74 +876,66 @@ def _counterfactual_layered(eng, params, dadj, triples, cand, K, toward, thresho
     """The search with one set_values + Engine.predict per evaluated variant and the kernels' rules on the host (any
     width and mode): the fused route's cross-check and its timing baseline.  Host arrays, counterfactual_search's
     keys."""
-    base = dadj.base_values.to(torch.float32)
     n, qp, thr = len(triples), cand["qptr"], np.float32(threshold)
     C = len(cand["entry"])
     out = dict(path=np.zeros((n, K + 1), np.float32), chosen=np.full((n, K), -1, np.int32),
                n_steps=np.zeros(n, np.int32), flipped=np.zeros(n, np.int32), cstep=np.full(C, -1, np.int32),
                loo=np.full(C, np.nan, np.float32))
-    entry = torch.as_tensor(cand["entry"].astype(np.int64), device=eng.device)
-    for q in range(n):
-        ed = eng.edges(triples[q][None])
-        a, b = int(qp[q]), int(qp[q + 1])
-        e, part, elig = entry[a:b], cand["partner"][a:b], cand["eligible"][a:b]
-        gone = np.zeros(b - a, bool)
+    with _EditedAdjacency(eng, dadj, triples, cand) as adj:
+        for q in range(n):
+            ed = adj.edges(q)
+            a, b = int(qp[q]), int(qp[q + 1])
+            e, part, elig = adj.entry[a:b], cand["partner"][a:b], cand["eligible"][a:b]
+            gone = np.zeros(b - a, bool)
 
-        def p_without(extra):
-            drop = gone.copy()
-            drop[list(extra)] = True
-            vals = base.clone()
-            vals[e[torch.as_tensor(np.flatnonzero(drop), device=eng.device)]] = 0
-            dadj.set_values(vals)
-            return np.float32(eng.predict(params, dadj, ed)[0].item())
+            def p_without(extra):
+                drop = gone.copy()
+                drop[list(extra)] = True
+                vals = adj.base.clone()
+                vals[e[torch.as_tensor(np.flatnonzero(drop), device=eng.device)]] = 0
+                dadj.set_values(vals)
+                return np.float32(eng.predict(params, dadj, ed)[0].item())
 
-        p = p_without(())
-        out["path"][q] = p
-        lower = bool(_lowering(p, toward, threshold))
-        crossed = lambda v: (not v > thr) if lower else bool(v > thr)  # noqa: E731
-        with_partner = lambda j: [j] + ([part[j]] if part[j] >= 0 else [])  # noqa: E731
-        live = np.flatnonzero(elig)
-        pj = np.array([p_without(with_partner(j)) for j in live], np.float32)
-        out["loo"][a + live] = pj
-        for i in range(K):
-            if crossed(p) or not len(live):
-                break
-            if i > 0:
-                pj = np.array([p_without(with_partner(j)) for j in live], np.float32)
-            best = int(np.lexsort((live, pj if lower else -pj))[0])
-            j, p = int(live[best]), pj[best]
-            gone[with_partner(j)] = True
-            out["cstep"][a + np.flatnonzero(gone & (out["cstep"][a:b] < 0))] = i
-            out["chosen"][q, i], out["path"][q, i + 1:], out["n_steps"][q] = j, p, i + 1
-            live = np.flatnonzero(elig & ~gone)
-        out["flipped"][q] = crossed(p)
-    dadj.set_values(base)
+            p = p_without(())
+            out["path"][q] = p
+            lower = bool(_lowering(p, toward, threshold))
+            crossed = lambda v: (not v > thr) if lower else bool(v > thr)  # noqa: E731
+            with_partner = lambda j: [j] + ([part[j]] if part[j] >= 0 else [])  # noqa: E731
+            live = np.flatnonzero(elig)
+            pj = np.array([p_without(with_partner(j)) for j in live], np.float32)
+            out["loo"][a + live] = pj
+            for i in range(K):
+                if crossed(p) or not len(live):
+                    break
+                if i > 0:
+                    pj = np.array([p_without(with_partner(j)) for j in live], np.float32)
+                best = int(np.lexsort((live, pj if lower else -pj))[0])
+                j, p = int(live[best]), pj[best]
+                gone[with_partner(j)] = True
+                out["cstep"][a + np.flatnonzero(gone & (out["cstep"][a:b] < 0))] = i
+                out["chosen"][q, i], out["path"][q, i + 1:], out["n_steps"][q] = j, p, i + 1
+                live = np.flatnonzero(elig & ~gone)
+            out["flipped"][q] = crossed(p)
     return out
 
 
 def _counterfactual_run(model, adjacency_data, test_triples, K, toward, threshold, undirected, exclude_target,
                         relations, fused, stats):
     """The shared body of counterfactual_batched and occlusion_batched: (triples, dadj, cand, result, fused, eng)."""
-    eng, params = _model_state(model)
-    N, R = model.num_entities, model.num_relations
-    triples = _as_triples(test_triples)
-    if len(triples) and (triples[:, 1].min() < 0 or triples[:, 1].max() >= R):
-        raise IddgcnError("triple relation index out of range [0, num_relations)")
     if not 0 <= K <= TOPK_MAX:
         raise IddgcnError(f"the search takes between 0 and {TOPK_MAX} steps, got {K}")
     _lowering(0.0, toward, threshold)
-    fused = eng.resolve_fused(fused, eng.per_query_ok(),
-                              "counterfactual search: the fused kernels take D in {32, 64}, fp32 features, "
-                              "1 <= R <= 8 and an unsharded engine: use fused=False for this model")
-    dadj = DeviceAdjacency(get_adj_mats(adjacency_data, N, R), N, eng.device)
+    eng, params, triples, fused, dadj = _fused_or_layered(
+        model, adjacency_data, test_triples, fused,
+        "counterfactual search: the fused kernels take D in {32, 64}, fp32 features, 1 <= R <= 8 and an unsharded "
+        "engine: use fused=False for this model")
     cand = counterfactual_candidates(dadj, triples, undirected, exclude_target, relations)
     if fused:
         with _launch_events(stats):
             res = eng.counterfactual_search(params, dadj, triples, cand, K, toward, threshold)
     else:
         res = _counterfactual_layered(eng, params, dadj, triples, cand, K, toward, threshold)
-    if stats is not None:
-        stats.update(fused=bool(fused), candidates=int(len(cand["entry"])))
+    _note_route(stats, fused, cand)
     return triples, dadj, cand, res, fused, eng
 
 
@@ -969,40 +998,20 @@ def occlusion_batched(model, adjacency_data, test_triples, top_k=10, *, toward="
     triples, dadj, cand, res, fused, eng = _counterfactual_run(model, adjacency_data, test_triples, 0, toward,
                                                                threshold, undirected, exclude_target, relations,
                                                                fused, stats)
-    n, qp, edges_of = len(triples), cand["qptr"], _candidate_edges(cand)
-    q_of = np.repeat(np.arange(n), np.diff(qp))
-    if fused:
+    n = len(triples)
+    q_of = np.repeat(np.arange(n), np.diff(cand["qptr"]))
+    p0 = res["path"][:, 0]
+    if fused:                                                      # the scores stay on the device
         dev = eng.device
-        p0 = res["path"][:, 0]
         sign = torch.as_tensor(np.where(_lowering(p0.cpu().numpy(), toward, threshold), 1.0, -1.0).astype(np.float32),
                                device=dev)
         qd = torch.as_tensor(q_of, device=dev)
         score = torch.where(torch.as_tensor(cand["eligible"], device=dev), sign[qd] * (p0[qd] - res["loo"]),
                             torch.full_like(res["loo"], -np.inf))
-        with eng._mark("occlusion_topk"):
-            te, tv, _ = ops.explain_topk(eng.to_device(qp, np.int64), eng.to_device(cand["entry"]), score, k)
-        te, tv = te.cpu().numpy().astype(np.int64), tv.cpu().numpy()
-        # entry id -> candidate: the segments ascend by entry id
-        total = dadj.total_nnz
-        ckey = q_of.astype(np.int64) * total + cand["entry"]
-        preds, scores = [], []
-        for q in range(n):
-            ok = np.isfinite(tv[q]) & (te[q] >= 0)
-            at = np.searchsorted(ckey, q * total + te[q][ok])
-            preds.append(edges_of[at])
-            scores.append(tv[q][ok])
-        return preds, scores
-    p0 = res["path"][:, 0]
-    sign = np.where(_lowering(p0, toward, threshold), 1.0, -1.0).astype(np.float32)
-    score = np.where(cand["eligible"], sign[q_of] * (p0[q_of] - res["loo"]), -np.inf).astype(np.float32)
-    preds, scores = [], []
-    for q in range(n):
-        a, b = qp[q], qp[q + 1]
-        o = np.lexsort((cand["entry"][a:b], -score[a:b]))
-        o = o[np.isfinite(score[a:b][o])][:k]
-        preds.append(edges_of[a:b][o])
-        scores.append(score[a:b][o])
-    return preds, scores
+    else:
+        sign = np.where(_lowering(p0, toward, threshold), 1.0, -1.0).astype(np.float32)
+        score = np.where(cand["eligible"], sign[q_of] * (p0[q_of] - res["loo"]), -np.inf).astype(np.float32)
+    return _rank_candidates(eng, dadj, cand, n, score, k, mark="occlusion_topk")
 
 
 def counterfactual_summary(result):
@@ -1092,31 +1101,27 @@ def _path_layered(eng, params, dadj, triples, cand, alpha, omega):
     """The path one node at a time on the layered kernels (any width and mode): per (triple, node) one set_values and
     Engine.value_grads, Engine.predict for the two end points.  The fused route's cross-check; device tensors."""
     dev = eng.device
-    base = dadj.base_values.to(torch.float32)
     n, qp = len(triples), cand["qptr"]
-    entry = torch.as_tensor(cand["entry"].astype(np.int64), device=dev)
     val = torch.as_tensor(cand["val"], device=dev)
     elig = torch.as_tensor(np.asarray(cand["eligible"], bool), device=dev)
     attr = torch.zeros(len(cand["entry"]), dtype=torch.float64, device=dev)
     ends = torch.empty(2, n, dtype=torch.float32, device=dev)
-    for q in range(n):
-        ed = eng.edges(triples[q][None])
-        sl = slice(int(qp[q]), int(qp[q + 1]))
-        e, v, el = entry[sl], val[sl], elig[sl]
-
-        def at(a):
-            vals = base.clone()
-            vals[e] = torch.where(el, v * a, v)
-            dadj.set_values(vals)
-
-        for i, a in enumerate((0.0, 1.0)):
-            at(a)
-            ends[i, q] = eng.predict(params, dadj, ed)[0]
-        for a, w in zip(alpha, omega):
-            at(float(np.float32(a)))
-            dv, _ = eng.value_grads(params, dadj, ed)
-            attr[sl] += float(np.float32(w)) * torch.cat(dv)[e].double()
-    dadj.set_values(base)
+    with _EditedAdjacency(eng, dadj, triples, cand) as adj:
+        for q in range(n):
+            ed = adj.edges(q)
+            sl = slice(int(qp[q]), int(qp[q + 1]))
+            e, v, el = adj.entry[sl], val[sl], elig[sl]
+            for i, a in enumerate((0.0, 1.0)):
+                vals = adj.base.clone()
+                vals[e] = torch.where(el, v * a, v)
+                dadj.set_values(vals)
+                ends[i, q] = eng.predict(params, dadj, ed)[0]
+            for a, w in zip(alpha, omega):
+                vals = adj.base.clone()
+                vals[e] = torch.where(el, v * float(np.float32(a)), v)
+                dadj.set_values(vals)
+                dv, _ = eng.value_grads(params, dadj, ed)
+                attr[sl] += float(np.float32(w)) * torch.cat(dv)[e].double()
     attr = torch.where(elig, attr * val.double(), torch.zeros_like(attr))
     q_of = torch.as_tensor(np.repeat(np.arange(n), np.diff(qp)), device=dev)
     total = torch.zeros(n, dtype=torch.float64, device=dev).index_add_(0, q_of, attr)
@@ -1124,15 +1129,15 @@ def _path_layered(eng, params, dadj, triples, cand, alpha, omega):
     return dict(attr=attr.float(), total=total.float(), p_full=ends[1], p_base=ends[0], gap=gap.float())
 
 
-def _rank_candidates(eng, dadj, cand, n, score, k):
+def _rank_candidates(eng, dadj, cand, n, score, k, mark="attribution_topk"):
     """occlusion_batched's ranking of per-candidate scores (-inf: not ranked): descending, ties by ascending entry id,
-    k_q = min(k, finite scores).  A device tensor is ranked by ops.explain_topk, a host array on the host.  Returns
-    (list of (k_q, 3) int64 edge arrays, list of (k_q,) fp32 scores)."""
+    k_q = min(k, finite scores).  A device tensor is ranked by ops.explain_topk (a launch marked ``mark``), a host
+    array on the host.  Returns (list of (k_q, 3) int64 edge arrays, list of (k_q,) fp32 scores)."""
     qp, edges_of = cand["qptr"], _candidate_edges(cand)
     q_of = np.repeat(np.arange(n), np.diff(qp))
     preds, scores = [], []
     if isinstance(score, torch.Tensor):
-        with eng._mark("attribution_topk"):
+        with eng._mark(mark):
             te, tv, _ = ops.explain_topk(eng.to_device(qp, np.int64), eng.to_device(cand["entry"]), score, k)
         te, tv = te.cpu().numpy().astype(np.int64), tv.cpu().numpy()
         # entry id -> candidate: the segments ascend by entry id
@@ -1181,10 +1186,6 @@ def integrated_gradients_batched(model, adjacency_data, test_triples, top_k=10, 
     k = int(top_k)
     if not 1 <= k <= TOPK_MAX:
         raise IddgcnError(f"top_k must be in [1, {TOPK_MAX}], got {top_k}")
-    N, R = model.num_entities, model.num_relations
-    triples = _as_triples(test_triples)
-    if len(triples) and (triples[:, 1].min() < 0 or triples[:, 1].max() >= R):
-        raise IddgcnError("triple relation index out of range [0, num_relations)")
     _lowering(0.0, toward, threshold)
     if nodes is not None:
         if tol is not None:
@@ -1196,13 +1197,12 @@ def integrated_gradients_batched(model, adjacency_data, test_triples, top_k=10, 
         quadrature_rule(steps, quadrature)                         # refuses a bad rule before any device work
         if tol is not None and not int(steps) <= int(max_steps) <= PATH_MAX_STEPS:
             raise IddgcnError(f"max_steps must lie in [steps, {PATH_MAX_STEPS}], got {max_steps}")
-    eng, params = _model_state(model)
-    fused = eng.resolve_fused(fused, eng.per_query_ok(),
-                              "integrated gradients: the fused kernels take D in {32, 64}, fp32 features, "
-                              "1 <= R <= 8 and an unsharded engine: use fused=False for this model")
-    dadj = DeviceAdjacency(get_adj_mats(adjacency_data, N, R), N, eng.device)
+    eng, params, triples, fused, dadj = _fused_or_layered(
+        model, adjacency_data, test_triples, fused,
+        "integrated gradients: the fused kernels take D in {32, 64}, fp32 features, 1 <= R <= 8 and an unsharded "
+        "engine: use fused=False for this model")
     cand = counterfactual_candidates(dadj, triples, False, exclude_target, relations)
-    n = len(triples)
+    n, R = len(triples), model.num_relations
 
     def run(idx, sub, alpha, omega):
         if fused:
@@ -1214,8 +1214,7 @@ def integrated_gradients_batched(model, adjacency_data, test_triples, top_k=10, 
             res, used, rounds = run(np.arange(n), cand, al, om), np.full(n, len(al), np.int64), 1
         else:
             res, used, rounds = _refine_by_gap(run, cand, n, steps, quadrature, tol, max_steps)
-    if stats is not None:
-        stats.update(fused=bool(fused), candidates=int(len(cand["entry"])), rounds=rounds)
+    _note_route(stats, fused, cand, rounds=rounds)
     host = {nm: v.cpu().numpy() for nm, v in res.items()}
     # the fused route ranks on the device (ops.explain_topk), the per-node route on the host
     rank = lambda s: _rank_candidates(eng, dadj, cand, n, torch.as_tensor(s, device=eng.device) if fused else s, k)  # noqa: E731

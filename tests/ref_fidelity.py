@@ -66,6 +66,15 @@ def make_params(N, R, D, rng, saturate=False):
     return {k: v.astype(np.float32) for k, v in p.items()}
 
 
+def model_with(params, N, R, D):
+    """An IDDGCN_Model of that size holding ``params`` (make_params' dict)."""
+    from iddgcn_amd import get_IDDGCN_Model
+    model = get_IDDGCN_Model(N, R, D, D, 123, None, 0, 0)
+    model._set_named(params)
+    model._invalidate()
+    return model
+
+
 def small_case(d, R, saturate=False, seed=0):
     """N = 50: 400 random triples over nodes 0..48 and the self loop (7, 0, 7); node 49 has no stored entry.  200
     queries with a repeated one, h == t and empty rows on either side.  Returns (N, adjacency triples, params, q)."""

@@ -25,13 +25,6 @@ N_ENT, N_REL = 845, 4
 _RUNS = {}
 
 
-def model_with(params, N, R, D):
-    model = get_IDDGCN_Model(N, R, D, D, 123, None, 0, 0)
-    model._set_named(params)
-    model._invalidate()
-    return model
-
-
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.int32)
 
@@ -55,7 +48,7 @@ def run(d, R, saturate, cuda, undirected=False):
     if key not in _RUNS:
         N, tri, params, q = RF.small_case(d, R, saturate)
         q = q[:NQ]
-        model = model_with(params, N, R, d)
+        model = RF.model_with(params, N, R, d)
         if (d, R, saturate) in RC.SEARCH_CASES:
             thr = RC.case(d, R, saturate)["threshold"]
         else:
@@ -165,7 +158,7 @@ def test_bitwise_tie_goes_to_the_lower_entry(cuda):
     for D in (32, 64):
         params = RF.make_params(N, R, D, rng)
         params["E"][5] = params["E"][3]
-        model = model_with(params, N, R, D)
+        model = RF.model_with(params, N, R, D)
         for toward, thr in (("lower", 0.0), ("raise", 1.0)):              # never crossed: both steps are taken
             res = X.counterfactual_batched(model, tri, q, 2, toward=toward, threshold=thr, relations=[1],
                                            return_occlusion=True)
@@ -349,7 +342,7 @@ def test_large_rows(D, big, cuda):
     assert np.diff(cand["qptr"]).tolist() == [big, 64, 127, 129] and big > (80 * 1024) // (4 * D)
     ref = RC.search(params, q, cand, 2, "lower", 0.0)
     assert ref["gap"].min() > 1e-5                                    # measured: 1.7e-5 at least, |p32 - p64| 1.2e-7
-    model = model_with(params, N, R, D)
+    model = RF.model_with(params, N, R, D)
     res = X.counterfactual_batched(model, tri, q, 2, toward="lower", threshold=0.0, fused=True)   # never crossed
     assert np.array_equal(res["chosen"], ref["chosen"])
     assert (res["n_edges"] == 2).all() and not res["flipped"].any()
@@ -416,7 +409,7 @@ def test_outside_the_envelope(cuda):
     N, tri, _, q = RF.small_case(64, 2)
     params = RF.make_params(N, 2, 128, np.random.default_rng(9))
     q = q[[0, 2, 3]]
-    model = model_with(params, N, 2, 128)
+    model = RF.model_with(params, N, 2, 128)
     with pytest.raises(L.IddgcnError, match="fused=False"):
         X.counterfactual_batched(model, tri, q, 2, fused=True)
     with pytest.raises(L.IddgcnError, match="fused=False"):

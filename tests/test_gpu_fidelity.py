@@ -24,13 +24,6 @@ N_ENT, N_REL = 845, 4
 _SMALL = {}
 
 
-def model_with(params, N, R, D):
-    model = get_IDDGCN_Model(N, R, D, D, 123, None, 0, 0)
-    model._set_named(params)
-    model._invalidate()
-    return model
-
-
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.int32)
 
@@ -45,7 +38,7 @@ def small(d, R, saturate, cuda):
         preds[1] = preds[0]                           # the repeated query, explained the same way
         cand = X.curve_steps(host, q, preds)
         assert cand["K"] == K
-        model = model_with(params, N, R, d)
+        model = RF.model_with(params, N, R, d)
         stats = {}
         ours = X.fidelity_curves(model, tri, q, preds, fused=True, stats=stats)
         assert stats["fused"] is True
@@ -166,7 +159,7 @@ def test_large_degrees(cuda):
     deg = np.diff(cand["qptr"])
     assert cand["K"] == L.TOPK_MAX and deg.tolist() == [64, 127, 129, 666, 601, 601, 601, 65] and deg.max() > 320
     assert (cand["rel"] < 2).all()                                    # the placeholder is no candidate
-    ours = X.fidelity_curves(model_with(params, N, R, D), tri, q, preds, fused=True)
+    ours = X.fidelity_curves(RF.model_with(params, N, R, D), tri, q, preds, fused=True)
     ref64 = RF.curves(params, q, cand, L.TOPK_MAX)
     ref32 = RF.curves(params, q, cand, L.TOPK_MAX, torch.float32)
     worst = check_against_restatement(ours, ref64, ref32, "large degrees")
@@ -221,7 +214,7 @@ def test_outside_the_envelope(cuda):
     host = DeviceAdjacency(get_adj_mats(tri, N, 2), N, "cpu")
     q = q[2:6]                                                        # h == t and the empty rows
     preds = RF.mixed_explanations(host, q)
-    model = model_with(params, N, 2, 128)
+    model = RF.model_with(params, N, 2, 128)
     with pytest.raises(L.IddgcnError, match="fused=False"):
         X.fidelity_curves(model, tri, q, preds, fused=True)
     stats = {}
@@ -231,7 +224,7 @@ def test_outside_the_envelope(cuda):
     ref = RF.curves(params, q, cand, cand["K"])
     assert np.abs(o["deletion"] - ref[0]).max() <= 1e-4 and np.abs(o["insertion"] - ref[1]).max() <= 1e-4
     assert np.abs(ref[0][:, -1] - ref[0][:, 0]).max() > 1e-3
-    model = model_with(RF.make_params(N, 2, 64, np.random.default_rng(9)), N, 2, 64)
+    model = RF.model_with(RF.make_params(N, 2, 64, np.random.default_rng(9)), N, 2, 64)
     eng = model._device_state()
     eng.features = "bf16"
     with pytest.raises(L.IddgcnError):

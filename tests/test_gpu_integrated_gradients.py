@@ -30,13 +30,6 @@ N_ENT, N_REL = 845, 4
 _SMALL = {}
 
 
-def model_with(params, N, R, D):
-    model = get_IDDGCN_Model(N, R, D, D, 123, None, 0, 0)
-    model._set_named(params)
-    model._invalidate()
-    return model
-
-
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.int32)
 
@@ -59,7 +52,7 @@ def small(d, R, saturate, cuda):
         host = DeviceAdjacency(mats, N, "cpu")
         cand = X.counterfactual_candidates(host, q)
         cand40 = X.counterfactual_candidates(host, q[:NQ])
-        model = model_with(params, N, R, d)
+        model = RF.model_with(params, N, R, d)
         _SMALL[key] = dict(N=N, tri=tri, mats=mats, params=params, q=q, host=host, cand=cand, cand40=cand40,
                            model=model, ours=run_engine(model, mats, q[:NQ], cand40, *GAUSS32),
                            ref64=RI.integrate(params, q[:NQ], cand40, *GAUSS32),
@@ -199,7 +192,7 @@ def test_long_rows(cuda):
     cand = X.counterfactual_candidates(DeviceAdjacency(mats, N, "cpu"), q)
     deg = np.diff(cand["qptr"])
     assert deg.tolist() == [64, 127, 129, 666, 601, 601, 601, 65] and (cand["rel"] < 2).all()
-    ours = run_engine(model_with(params, N, R, D), mats, q, cand, *GAUSS32)
+    ours = run_engine(RF.model_with(params, N, R, D), mats, q, cand, *GAUSS32)
     ref64 = RI.integrate(params, q, cand, *GAUSS32)
     ref32 = RI.integrate(params, q, cand, *GAUSS32, dtype=torch.float32)
     check_against_restatement(ours, ref64, ref32, cand, "long rows")
@@ -262,7 +255,7 @@ def test_routes(cuda):
     for a, b in zip(fused["edges"], layered["edges"]):
         assert a.shape == b.shape
     N, tri = c["N"], c["tri"]
-    model = model_with(RF.make_params(N, 2, 128, np.random.default_rng(9)), N, 2, 128)
+    model = RF.model_with(RF.make_params(N, 2, 128, np.random.default_rng(9)), N, 2, 128)
     tri2 = tri[tri[:, 1] < 2]
     q2 = np.array([(7, 0, 7), (5, 0, 49), (3, 1, 8)], np.int64)
     with pytest.raises(L.IddgcnError, match="fused=False"):

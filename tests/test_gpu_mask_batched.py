@@ -14,6 +14,7 @@ from iddgcn_amd import explain as X
 from iddgcn_amd import get_IDDGCN_Model
 from iddgcn_amd.graph import get_adj_mats
 from oracle import ref_explain
+from tests import ref_fidelity as RF
 from tests.test_mask_batched_host import EMPTY, N_ENT, N_REL, fold4_case, make_params, synthetic_case
 
 pytestmark = pytest.mark.gpu
@@ -36,13 +37,6 @@ def kind_kw(kind, R):
         return dict(num_epochs=5, threshold=0.2)
     ratios = np.arange(R, 0, -1, dtype=np.float64)
     return dict(num_epochs=10, threshold=0.15, target_ratios=tuple(ratios / ratios.sum()))
-
-
-def model_with(params, N, R, D):
-    model = get_IDDGCN_Model(N, R, D, D, 123, None, 0, 0)
-    model._set_named(params)
-    model._invalidate()
-    return model
 
 
 def check_against_oracle(ours, ref, what=""):
@@ -81,7 +75,7 @@ def synthetic_run(D, R, kind, cuda):
             q = np.delete(q, EMPTY, 0)
         kw = kind_kw(kind, R)
         ref = ref_explain.mask_explainer(params, tri, q, N, R, init, **kw)
-        model = model_with(params, N, R, D)
+        model = RF.model_with(params, N, R, D)
         stats = {}
         ours = X.mask_explainer_batched(model, tri, q, init_value=init, return_masks=True, stats=stats, **kw)
         _SYN[key] = dict(model=model, tri=tri, q=q, init=init, kw=kw, ref=ref, ours=ours, stats=stats)
@@ -161,7 +155,7 @@ def test_large_degrees(kind, cuda):
     q = np.array([(1, 0, 2), (2, 1, 3), (3, 0, 4), (4, 1, 5), (5, 0, 6), (6, 1, 5), (5, 0, 5), (3, 1, 1)], np.int64)
     kw = kind_kw(kind, R)
     ref = ref_explain.mask_explainer(params, tri, q, N, R, init, **kw)
-    model = model_with(params, N, R, D)
+    model = RF.model_with(params, N, R, D)
     stats = {}
     ours = X.mask_explainer_batched(model, tri, q, init_value=init, return_masks=True, stats=stats, **kw)
     worst = check_against_oracle(ours, ref, f"large degrees {kind}")

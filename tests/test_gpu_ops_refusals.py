@@ -3,14 +3,21 @@ with contiguous rows, a CSR pointer that ascends, the three layers' K / S / Wa /
 bf16 entry pair, the Adam size loop, a given output) per wrapper that has it, plus a wrong dtype, a wrong shape and a
 non-contiguous tensor for one argument of each of those wrappers.  Every case is refused with IddgcnError before
 anything is launched, and ``match`` is the offending argument as the message names it: the intended check fired, not an
-earlier one.  Shapes are the smallest that express a check (N = 8, R = 2, D = 32, six edges, two queries)."""
+earlier one.  Shapes are the smallest that express a check (N = 8, R = 2, D = 32, six edges, two queries).
+
+test_engine_candidate_refusals: the checks one level up, in the three Engine methods that take a candidate table
+(tests/candidate_cases.py), with the whole message compared."""
 import types
 
+import numpy as np
 import pytest
 import torch
 
 from iddgcn_amd import _lib as L
 from iddgcn_amd import ops
+from iddgcn_amd.graph import DeviceAdjacency, get_adj_mats
+from tests import candidate_cases as CC
+from tests import ref_fidelity as RF
 
 pytestmark = pytest.mark.gpu
 N, R, D, M, Q, C, K_TOP = 8, 2, 32, 6, 2, 5, 3
@@ -255,3 +262,74 @@ def test_refused(call, match, ranges, g, monkeypatch):
     monkeypatch.setattr(ops, "CHECK_INDEX_RANGES", ranges)
     with pytest.raises(L.IddgcnError, match=match):
         call(g)
+
+
+ENVELOPE = {"edit_curves": "edit_curves takes D in {32, 64}, fp32 features, 1 <= R <= 8 and an unsharded engine: use "
+                           "explain.fidelity_curves(fused=False) for this engine",
+            "counterfactual_search": "counterfactual_search takes D in {32, 64}, fp32 features, 1 <= R <= 8 and an "
+                                     "unsharded engine: use explain.counterfactual_batched(fused=False) for this engine",
+            "integrated_gradients": "integrated_gradients takes D in {32, 64}, fp32 features, 1 <= R <= 8 and an "
+                                    "unsharded engine: use explain.integrated_gradients_batched(fused=False) for this "
+                                    "engine"}
+
+
+def test_engine_candidate_refusals(cuda):
+    """Engine.edit_curves / counterfactual_search / integrated_gradients refuse a malformed call before any launch,
+    with the exception type and the whole message of the table; then a good call of each returns its shapes."""
+    assert (CC.N, CC.R, CC.Q, CC.C) == (N, R, Q, C)
+    K = CC.K
+    tri = np.array([[0, 0, 1], [1, 1, 2], [2, 0, 3], [3, 1, 0]], np.int64)
+    rule = (np.array([0.25, 0.75]), np.array([0.5, 0.5]))
+
+    def setup(n, d):
+        model = RF.model_with(RF.make_params(n, R, d, np.random.default_rng(5)), n, R, d)
+        eng = model._device_state()
+        return eng, model._params
+
+    eng, params = setup(N, D)
+    dadj = DeviceAdjacency(get_adj_mats(tri, N, R), N, eng.device)
+
+    def call(who, cand, eng=eng, params=params, adj=dadj, q=CC.TRIPLES, K=K, rule=rule, **kw):
+        args = (K,) if who != "integrated_gradients" else rule
+        return getattr(eng, who)(params, adj, q, cand, *args, **kw)
+
+    def refused(kind, message, who, cand=None, **kw):
+        with pytest.raises(kind) as e:
+            call(who, CC.base(who) if cand is None else cand, **kw)
+        assert type(e.value) is kind and str(e.value) == message, (who, kw, str(e.value))
+
+    accepted = []
+    for name, who, cand, message in CC.cases():
+        if message is None:
+            accepted.append((name, who, cand))
+        else:
+            refused(L.IddgcnError, message, who, cand)
+    other_adj = DeviceAdjacency(get_adj_mats(tri, N + 1, R), N + 1, eng.device)
+    big_eng, big_params = setup(N, 128)
+    for who in CC.EXTRA:
+        refused(L.IddgcnError, f"{who}: the adjacency is not this engine's size", who, adj=other_adj)
+        refused(ValueError, "max_entries must be positive, got 0", who, max_entries=0)
+        refused(L.IddgcnError, "triple entity index out of range [0, num_entities)", who,
+                q=np.array([[0, 0, 2], [1, 1, N]], np.int64))
+        refused(L.IddgcnError, ENVELOPE[who], who, eng=big_eng, params=big_params)
+    for k in (0, 65):
+        refused(L.IddgcnError, f"edit_curves: K must be in [1, 64], got {k}", "edit_curves", K=k)
+    for k in (-1, 65):
+        refused(L.IddgcnError, f"counterfactual_search: K must be in [0, 64], got {k}", "counterfactual_search", K=k)
+    for m_alpha, m_omega in ((2, 3), (0, 0), (1025, 1025)):
+        refused(L.IddgcnError, "integrated_gradients: alpha and omega must be (m,) with m in [1, 1024]",
+                "integrated_gradients", rule=(np.full(m_alpha, 0.5), np.full(m_omega, 1.0 / max(m_omega, 1))))
+
+    def shapes(out):
+        return {k: tuple(v.shape) for k, v in out.items()} if isinstance(out, dict) else [tuple(v.shape) for v in out]
+
+    for name, who, cand in accepted:
+        none = {k: (v[:1] if k == "qptr" else v[:0]) for k, v in cand.items()}          # the same call of no query
+        for q, cd in ((CC.TRIPLES, cand), (CC.TRIPLES[:0], none)):
+            n, c = len(q), len(cd["rel"])
+            want = {"edit_curves": [(n, K + 1), (n, K + 1)],
+                    "counterfactual_search": dict(path=(n, K + 1), chosen=(n, K), n_steps=(n,), flipped=(n,),
+                                                  cstep=(c,), loo=(c,)),
+                    "integrated_gradients": dict(attr=(c,), total=(n,), p_full=(n,), p_base=(n,), gap=(n,))}[who]
+            assert shapes(call(who, cd, q=q)) == want, (name, n)
+    torch.cuda.synchronize()
