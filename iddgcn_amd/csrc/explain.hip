@@ -26,6 +26,7 @@
 // nodes per workgroup.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "iddgcn.h"
@@ -485,6 +486,58 @@ __device__ __forceinline__ float matvec1(const float* __restrict__ Mk, const flo
     return (c4[0] + c4[1]) + (c4[2] + c4[3]);
 }
 
+// What the four fused kernels below share, written once.  Each is an inline function of LDS / global pointers the
+// caller owns; the rule for these kernels is bitwise results within the same register and LDS budget
+// (profiles/r21/), so an output element keeps its expression, its chain split and its candidate order here.
+
+// the relation segments of a query's candidate list (ascending by relation): rstart[r] = the first candidate of a
+// relation >= r.  Candidate j's part of the scan; rstart[0 .. MAX_R] starts at n
+__device__ __forceinline__ void rstart_mark(int* rstart, const int* crel, int j) {
+    const int r1 = crel[j];
+    const int r0 = j ? crel[j - 1] : -1;
+    for (int r = r0 + 1; r <= r1; ++r) rstart[r] = j;
+}
+
+// the whole scan; the caller's next barrier publishes it
+__device__ __forceinline__ void rstart_scan(int* rstart, const int* crel, int n) {
+    if (threadIdx.x <= MAX_R) rstart[threadIdx.x] = n;
+    __syncthreads();
+    for (int j = threadIdx.x; j < n; j += NT) rstart_mark(rstart, crel, j);
+}
+
+// es <- the E rows of the first min(n, ROWS) candidates
+template <int D, int ROWS>
+__device__ __forceinline__ void stage_es(float* es, const float* __restrict__ E, const int* ccol, int n) {
+    const int ns = n < ROWS ? n : ROWS;
+    for (int idx = threadIdx.x; idx < ns * D; idx += NT) es[idx] = E[(size_t)ccol[idx / D] * D + idx % D];
+}
+
+// element i of the softmax over the logits zs[0 .. R): the max, the sum of expf, expf(z - max) / sum, in that order
+__device__ __forceinline__ float rel_softmax(const float* zs, int R, int i) {
+    float mx = -INFINITY;
+    for (int r = 0; r < R; ++r) mx = fmaxf(mx, zs[r]);
+    float sum = 0.f;
+    for (int r = 0; r < R; ++r) sum += expf(zs[r] - mx);
+    return expf(zs[i] - mx) / sum;
+}
+
+// its backward: du_i from the softmax values sm and the gradient da w.r.t. them
+__device__ __forceinline__ float rel_softmax_bwd(const float* sm, const float* da, int R, int i) {
+    float sum = 0.f;
+    for (int r = 0; r < R; ++r) sum = fmaf(sm[r], da[r], sum);
+    return sm[i] * (da[i] - sum);
+}
+
+// column k of dx^{l-1} = dz S^l^T (+ du Walpha^l^T on the head side): STk = S^l^T + k, wa = row k of Walpha^l
+template <int D>
+__device__ __forceinline__ float dx_step(const float* STk, const float* dz, bool head, const float* du,
+                                         const float* wa, int R) {
+    float acc = matvec1<D>(STk, dz);
+    if (head)
+        for (int r = 0; r < R; ++r) acc = fmaf(du[r], wa[r], acc);
+    return acc;
+}
+
 template <int D>
 __global__ __launch_bounds__(NT) void mask_explain_kernel(const iddgcn_mask_explain_t a) {
     constexpr int GR = NT / D;                 // groups of D lanes: 4 / 8
@@ -537,15 +590,10 @@ __global__ __launch_bounds__(NT) void mask_explain_kernel(const iddgcn_mask_expl
             a.v[e] *= powf(a.b2, (float)gap);
         }
         mk[j] = a.init_e[e];
-        const int r1 = crel[j];
-        const int r0 = j ? crel[j - 1] : -1;
-        for (int r = r0 + 1; r <= r1; ++r) rstart[r] = j;
+        rstart_mark(rstart, crel, j);
     }
     if (tid < 2 * D) x[0][side2][k] = a.E[(size_t)(side2 ? tt : hh) * D + k];
-    {
-        const int ns = n < ES_ROWS ? n : ES_ROWS;
-        for (int idx = tid; idx < ns * D; idx += NT) es[idx] = a.E[(size_t)ccol[idx / D] * D + idx % D];
-    }
+    stage_es<D, ES_ROWS>(es, a.E, ccol, n);
     __syncthreads();
 
     for (int ep = -1; ep < a.num_epochs; ++ep) {
@@ -619,11 +667,7 @@ __global__ __launch_bounds__(NT) void mask_explain_kernel(const iddgcn_mask_expl
             }
             __syncthreads();
             if (tid < R) {
-                float mx = -INFINITY;
-                for (int i = 0; i < R; ++i) mx = fmaxf(mx, zs[i]);
-                float sum = 0.f;
-                for (int i = 0; i < R; ++i) sum += expf(zs[i] - mx);
-                const float s = expf(zs[tid] - mx) / sum;
+                const float s = rel_softmax(zs, R, tid);
                 sm[l][tid] = s;
                 w[l][tid] = sigmoid_ref(s);
             }
@@ -695,21 +739,11 @@ __global__ __launch_bounds__(NT) void mask_explain_kernel(const iddgcn_mask_expl
             if (l == 0) break;
             __syncthreads();
             // through the softmax
-            if (tid < R) {
-                float sum = 0.f;
-                for (int i = 0; i < R; ++i) sum = fmaf(sm[l][i], da[i], sum);
-                du[tid] = sm[l][tid] * (da[tid] - sum);
-            }
+            if (tid < R) du[tid] = rel_softmax_bwd(sm[l], da, R, tid);
             __syncthreads();
-            // dx^{l-1} = dz S^l^T (+ du Walpha^l^T on the head side), from the transposed S
-            if (tid < 2 * D) {
-                float acc = matvec1<D>(a.ST[l] + k, dz[side2]);
-                if (side2 == 0) {
-                    const float* wa = a.Wa[l] + (size_t)k * R;
-                    for (int r = 0; r < R; ++r) acc = fmaf(du[r], wa[r], acc);
-                }
-                dx[side2][k] = acc;
-            }
+            // dx^{l-1} = dz S^l^T (+ du Walpha^l^T on the head side), from the transposed S in global memory
+            if (tid < 2 * D)
+                dx[side2][k] = dx_step<D>(a.ST[l] + k, dz[side2], side2 == 0, du, a.Wa[l] + (size_t)k * R, R);
             __syncthreads();
         }
 #pragma unroll
@@ -799,308 +833,246 @@ __device__ __forceinline__ void matvec_rows(const float* __restrict__ Mk, const 
     for (int j = 0; j < NR; ++j) y[j] = (c4[j][0] + c4[j][1]) + (c4[j][2] + c4[j][3]);
 }
 
+// The variant tile of curves_kernel and cf_step_kernel: its LDS block and every step from the staging to a variant's
+// score, written once, so that the two kernels run one forward (tests/test_gpu_counterfactual.py holds their outputs
+// equal bit for bit).  A kernel adds its variant table, its keep rule and its store rule.  `a` is the kernel's
+// argument struct (E, rel, the candidate arrays, the layers' K, S, Wa, ba), c0 the start of the query's candidates.
 template <int D>
-__global__ __launch_bounds__(NT) void curves_kernel(const iddgcn_explain_curves_t a, int n_tiles) {
-    constexpr int GR = NT / D;                 // groups of D lanes: 4 / 8
-    constexpr int RPG = MAX_R / GR;            // relations per group: 2 / 1
-    constexpr int RW = CV_ROWS / GR;           // rows per group in the combine: 4 / 2
-    constexpr int ES_ROWS = CV_ES_BYTES / (4 * D);
-    __shared__ float es[ES_ROWS * D];
-    __shared__ __attribute__((aligned(16))) float AE[MAX_R][CV_ROWS][D];
-    __shared__ float P[MAX_R][CV_ROWS][D];
-    __shared__ __attribute__((aligned(16))) float x[2][CV_ROWS][D];
-    __shared__ float zs[CV_VT][MAX_R];
-    __shared__ float w[CV_VT][MAX_R];
-    __shared__ int rstart[MAX_R + 1];
+struct Tile {
+    static constexpr int GR = NT / D;                 // groups of D lanes: 4 / 8
+    static constexpr int RPG = MAX_R / GR;            // relations per group: 2 / 1
+    static constexpr int RW = CV_ROWS / GR;           // rows per group in the combine: 4 / 2
+    static constexpr int ES_ROWS = CV_ES_BYTES / (4 * D);
+    float es[ES_ROWS * D];
+    float AE[MAX_R][CV_ROWS][D];               // AE and x are read 16 bytes at a time: a kernel declares the block
+    float P[MAX_R][CV_ROWS][D];                // aligned(16), and their offsets are multiples of 16 (tile_forward)
+    float x[2][CV_ROWS][D];
+    float zs[CV_VT][MAX_R];
+    float w[CV_VT][MAX_R];
+    int rstart[MAX_R + 1];
+};
 
-    const int tid = threadIdx.x;
-    const int R = a.R;
-    const int q = blockIdx.x / n_tiles;
-    const int v0 = (blockIdx.x % n_tiles) * CV_VT;
-    const int nv = 2 * (a.k + 1);              // variants 0 .. k: deletion points, k + 1 .. 2 k + 1: insertion points
-    const int hh = a.h[q], rr = a.r[q], tt = a.t[q];
-    const long long c0 = a.qptr[q];
-    const int n = (int)(a.qptr[q + 1] - c0);
-    const int* crel = a.crel + c0;
+// with `stage` (once per workgroup): the relation segments of the candidate list and the staged E rows; then
+// x^0 = E[h] / E[t] in every variant, and the barrier that publishes all of it
+template <int D, class A>
+__device__ __forceinline__ void tile_begin(Tile<D>& T, const A& a, long long c0, int n, int hh, int tt, bool stage) {
+    if (stage) {
+        rstart_scan(T.rstart, a.crel + c0, n);
+        stage_es<D, Tile<D>::ES_ROWS>(T.es, a.E, a.ccol + c0, n);
+    }
+    for (int idx = threadIdx.x; idx < CV_ROWS * D; idx += NT) {
+        const int row = idx / D;
+        T.x[0][row][idx % D] = a.E[(size_t)((row & 1) ? tt : hh) * D + idx % D];
+    }
+    __syncthreads();
+}
+
+// AE rows of every variant: candidates ascending, one chain per (row, relation, column).  keep(j, kp), called once per
+// candidate, says which of the tile's variants keep it; a candidate a variant drops (or that does not feed the side)
+// enters with a zero multiplier: fmaf(0, e, acc) is acc
+template <int D, class A, class Keep>
+__device__ __forceinline__ void tile_ae(Tile<D>& T, const A& a, long long c0, const Keep& keep) {
+    constexpr int GR = Tile<D>::GR, ES_ROWS = Tile<D>::ES_ROWS;
+    const int k = threadIdx.x % D, grp = threadIdx.x / D;
     const int* ccol = a.ccol + c0;
     const int* crole = a.crole + c0;
-    const int* cstep = a.cstep + c0;
     const float* cval = a.cval + c0;
-    const int k = tid % D, grp = tid / D;
-
-    // variants past the last repeat it (computed, never stored)
-    int pt[CV_VT];
-    bool isins[CV_VT];
 #pragma unroll
-    for (int u = 0; u < CV_VT; ++u) {
-        const int vi = v0 + u < nv ? v0 + u : nv - 1;
-        isins[u] = vi > a.k;
-        pt[u] = isins[u] ? vi - (a.k + 1) : vi;
-    }
-
-    // the relation segments of the candidate list, x^0 = E[h] / E[t] in every variant, the staged E rows
-    if (tid <= MAX_R) rstart[tid] = n;
-    __syncthreads();
-    for (int j = tid; j < n; j += NT) {
-        const int r1 = crel[j];
-        const int r0 = j ? crel[j - 1] : -1;
-        for (int r = r0 + 1; r <= r1; ++r) rstart[r] = j;
-    }
-    for (int idx = tid; idx < CV_ROWS * D; idx += NT) {
-        const int row = idx / D;
-        x[0][row][idx % D] = a.E[(size_t)((row & 1) ? tt : hh) * D + idx % D];
-    }
-    {
-        const int ns = n < ES_ROWS ? n : ES_ROWS;
-        for (int idx = tid; idx < ns * D; idx += NT) es[idx] = a.E[(size_t)ccol[idx / D] * D + idx % D];
-    }
-    __syncthreads();
-
-    // AE rows of every variant: candidates ascending, one chain per (row, relation, column); a candidate the variant
-    // drops (or that does not feed the side) enters with a zero multiplier: fmaf(0, e, acc) is acc
-#pragma unroll
-    for (int ri = 0; ri < RPG; ++ri) {
+    for (int ri = 0; ri < Tile<D>::RPG; ++ri) {
         const int r = grp + ri * GR;
-        if (r < R) {
+        if (r < a.R) {
             float acc[CV_ROWS];
 #pragma unroll
             for (int j = 0; j < CV_ROWS; ++j) acc[j] = 0.f;
-            const int j1 = rstart[r + 1];
-            for (int j = rstart[r]; j < j1; ++j) {
+            const int j1 = T.rstart[r + 1];
+            for (int j = T.rstart[r]; j < j1; ++j) {
                 const float val = cval[j];
-                const int st = cstep[j], role = crole[j];
-                const float ev = j < ES_ROWS ? es[j * D + k] : a.E[(size_t)ccol[j] * D + k];
+                const int role = crole[j];
+                bool kp[CV_VT];
+                keep(j, kp);
+                const float ev = j < ES_ROWS ? T.es[j * D + k] : a.E[(size_t)ccol[j] * D + k];
                 const float vh = (role & 1) ? val : 0.f, vt = (role & 2) ? val : 0.f;
 #pragma unroll
                 for (int u = 0; u < CV_VT; ++u) {
-                    const bool flipped = st >= 0 && st < pt[u];
-                    const bool keep = flipped == isins[u];
-                    acc[2 * u] = fmaf(keep ? vh : 0.f, ev, acc[2 * u]);
-                    acc[2 * u + 1] = fmaf(keep ? vt : 0.f, ev, acc[2 * u + 1]);
+                    acc[2 * u] = fmaf(kp[u] ? vh : 0.f, ev, acc[2 * u]);
+                    acc[2 * u + 1] = fmaf(kp[u] ? vt : 0.f, ev, acc[2 * u + 1]);
                 }
             }
 #pragma unroll
-            for (int j = 0; j < CV_ROWS; ++j) AE[r][j][k] = acc[j];
+            for (int j = 0; j < CV_ROWS; ++j) T.AE[r][j][k] = acc[j];
         }
     }
     __syncthreads();
+}
 
-    // forward: the reference layer on the CV_ROWS rows
+// forward: the reference layer on the CV_ROWS rows, three times; x^3 is left in x[1], behind a barrier
+template <int D, class A>
+__device__ __forceinline__ void tile_forward(Tile<D>& T, const A& a) {
+    static_assert(offsetof(Tile<D>, AE) % 16 == 0 && offsetof(Tile<D>, x) % 16 == 0, "matvec_rows reads f32x4");
+    constexpr int GR = Tile<D>::GR, RW = Tile<D>::RW;
+    const int tid = threadIdx.x, k = tid % D, grp = tid / D;
+    const int R = a.R;
     for (int l = 0; l < 3; ++l) {
         const int cur = l & 1;
         for (int item = grp; item < CV_VT * R; item += GR) {
             const int u = item / R, r = item % R;
-            const float z = group_sum<D>(x[cur][2 * u][k] * a.Wa[l][(size_t)k * R + r]);
-            if (k == 0) zs[u][r] = z + a.ba[l][r];
+            const float z = group_sum<D>(T.x[cur][2 * u][k] * a.Wa[l][(size_t)k * R + r]);
+            if (k == 0) T.zs[u][r] = z + a.ba[l][r];
         }
 #pragma unroll
-        for (int ri = 0; ri < RPG; ++ri) {
+        for (int ri = 0; ri < Tile<D>::RPG; ++ri) {
             const int r = grp + ri * GR;
             if (r < R) {
                 float y[CV_ROWS];
-                matvec_rows<D, CV_ROWS>(a.K[l] + (size_t)r * D * D + k, &AE[r][0][0], D, y);
+                matvec_rows<D, CV_ROWS>(a.K[l] + (size_t)r * D * D + k, &T.AE[r][0][0], D, y);
 #pragma unroll
-                for (int j = 0; j < CV_ROWS; ++j) P[r][j][k] = y[j];
+                for (int j = 0; j < CV_ROWS; ++j) T.P[r][j][k] = y[j];
             }
         }
         __syncthreads();
-        if (tid < CV_VT * R) {
-            const int u = tid / R, r = tid % R;
-            float mx = -INFINITY;
-            for (int i = 0; i < R; ++i) mx = fmaxf(mx, zs[u][i]);
-            float sum = 0.f;
-            for (int i = 0; i < R; ++i) sum += expf(zs[u][i] - mx);
-            w[u][r] = sigmoid_ref(expf(zs[u][r] - mx) / sum);
-        }
+        if (tid < CV_VT * R) T.w[tid / R][tid % R] = sigmoid_ref(rel_softmax(T.zs[tid / R], R, tid % R));
         __syncthreads();
         {
             float y[RW];
-            matvec_rows<D, RW>(a.S[l] + k, &x[cur][grp * RW][0], D, y);
+            matvec_rows<D, RW>(a.S[l] + k, &T.x[cur][grp * RW][0], D, y);
 #pragma unroll
             for (int j = 0; j < RW; ++j) {
                 const int row = grp * RW + j;
                 float v = y[j];
-                for (int r = 0; r < R; ++r) v = fmaf(w[row >> 1][r], P[r][row][k], v);
-                x[1 - cur][row][k] = sigmoid_ref(v);
+                for (int r = 0; r < R; ++r) v = fmaf(T.w[row >> 1][r], T.P[r][row][k], v);
+                T.x[1 - cur][row][k] = sigmoid_ref(v);
             }
         }
         __syncthreads();
     }
+}
 
-    // DistMult of every variant (x^3 sits in x[1])
-    for (int u = grp; u < CV_VT; u += GR) {
-        const float s = group_sum<D>(x[1][2 * u][k] * a.rel[(size_t)rr * D + k] * x[1][2 * u + 1][k]);
+// the DistMult score of variant u against the relation row rl, the same value in every lane of the calling group
+template <int D>
+__device__ __forceinline__ float tile_score(const Tile<D>& T, const float* rl, int u) {
+    const int k = threadIdx.x % D;
+    return sigmoid_ref(group_sum<D>(T.x[1][2 * u][k] * rl[k] * T.x[1][2 * u + 1][k]));
+}
+
+// curves_kernel's variants: 0 .. k are the deletion points, k + 1 .. 2 k + 1 the insertion points.  Variant u keeps a
+// candidate when "flipped within the first pt[u] steps" equals isins[u]
+struct CurvesKeep {
+    const int* cstep;
+    int pt[CV_VT];
+    bool isins[CV_VT];
+    __device__ __forceinline__ void operator()(int j, bool* kp) const {
+        const int st = cstep[j];
+#pragma unroll
+        for (int u = 0; u < CV_VT; ++u) kp[u] = (st >= 0 && st < pt[u]) == isins[u];
+    }
+};
+
+template <int D>
+__global__ __launch_bounds__(NT) void curves_kernel(const iddgcn_explain_curves_t a, int n_tiles) {
+    __shared__ __attribute__((aligned(16))) Tile<D> T;
+    const int q = blockIdx.x / n_tiles;
+    const int v0 = (blockIdx.x % n_tiles) * CV_VT;
+    const int nv = 2 * (a.k + 1);
+    const long long c0 = a.qptr[q];
+    const int n = (int)(a.qptr[q + 1] - c0);
+    const float* rl = a.rel + (size_t)a.r[q] * D;
+
+    // variants past the last repeat it (computed, never stored)
+    CurvesKeep keep;
+    keep.cstep = a.cstep + c0;
+#pragma unroll
+    for (int u = 0; u < CV_VT; ++u) {
+        const int vi = v0 + u < nv ? v0 + u : nv - 1;
+        keep.isins[u] = vi > a.k;
+        keep.pt[u] = keep.isins[u] ? vi - (a.k + 1) : vi;
+    }
+
+    tile_begin<D>(T, a, c0, n, a.h[q], a.t[q], true);
+    tile_ae<D>(T, a, c0, keep);
+    tile_forward<D>(T, a);
+    for (int u = threadIdx.x / D; u < CV_VT; u += Tile<D>::GR) {
+        const float p = tile_score<D>(T, rl, u);
         const int vi = v0 + u;
-        if (k == 0 && vi < nv) {
+        if (threadIdx.x % D == 0 && vi < nv) {
             float* out = vi > a.k ? a.ins + (size_t)q * (a.k + 1) + (vi - (a.k + 1)) : a.del + (size_t)q * (a.k + 1) + vi;
-            *out = sigmoid_ref(s);
+            *out = p;
         }
     }
 }
 
 // ---- counterfactual search -------------------------------------------------------------------------------------
-// cf_step_kernel: curves_kernel's sibling for step `step` of the greedy search: same staging, same AE chains, same
-// forward (written out again: curves_kernel keeps its machine code), another keep predicate.  With F the candidates
-// removed so far (cstep >= 0; nothing at step 0, where cstep is not read), variant 0 is F itself and variant 1 + j
-// drops candidate j and its partner too.  A variant is stored when it is the base at step 0 (path[q][0]) or an
-// eligible candidate outside F (vals[j]); the others are computed and dropped.  Workgroup b of a query's `tiles` takes
-// the tiles b, b + tiles, .. of 8 variants, so the E rows are staged once and the grid need not know the segment's
-// length.  LDS: curves_kernel's 152.5 KB at D = 64 and nothing more (the variant table lives in registers).
+// cf_step_kernel: step `step` of the greedy search on curves_kernel's tile (Tile and the tile_ functions above: one
+// LDS block, one staging, one set of AE chains, one forward for both kernels), with its own variants.  With F the
+// candidates removed so far (cstep >= 0; nothing at step 0, where cstep is not initialised and not read), variant 0 is
+// F itself and variant 1 + j drops candidate j and its partner too.  A variant is stored when it is the base at step 0
+// (path[q][0]) or an eligible candidate outside F (vals[j]); the others are computed and dropped.  Workgroup b of a
+// query's `tiles` takes the tiles b, b + tiles, .. of 8 variants, so the E rows are staged once and the grid need not
+// know the segment's length.  The variant table lives in registers.
+struct CfKeep {
+    const int* cstep;
+    bool later;                                // step > 0
+    int jv[CV_VT], pv[CV_VT];                  // the candidate a variant drops and its partner, -1: none
+    __device__ __forceinline__ void operator()(int j, bool* kp) const {
+        const bool gone = later && cstep[j] >= 0;
+#pragma unroll
+        for (int u = 0; u < CV_VT; ++u) kp[u] = !gone && j != jv[u] && j != pv[u];
+    }
+};
+
 template <int D>
 __global__ __launch_bounds__(NT) void cf_step_kernel(const iddgcn_counterfactual_t a, int step, int tiles,
                                                      float* __restrict__ vals) {
-    constexpr int GR = NT / D;
-    constexpr int RPG = MAX_R / GR;
-    constexpr int RW = CV_ROWS / GR;
-    constexpr int ES_ROWS = CV_ES_BYTES / (4 * D);
-    __shared__ float es[ES_ROWS * D];
-    __shared__ __attribute__((aligned(16))) float AE[MAX_R][CV_ROWS][D];
-    __shared__ float P[MAX_R][CV_ROWS][D];
-    __shared__ __attribute__((aligned(16))) float x[2][CV_ROWS][D];
-    __shared__ float zs[CV_VT][MAX_R];
-    __shared__ float w[CV_VT][MAX_R];
-    __shared__ int rstart[MAX_R + 1];
-
-    const int tid = threadIdx.x;
-    const int R = a.R;
+    __shared__ __attribute__((aligned(16))) Tile<D> T;
     const int q = blockIdx.x / tiles;
     // a query that has stopped: flipped, or the step before this one was not taken
     if (step > 0 && (a.flipped[q] || a.n_steps[q] != step)) return;
-    const int hh = a.h[q], rr = a.r[q], tt = a.t[q];
+    const int hh = a.h[q], tt = a.t[q];
+    const float* rl = a.rel + (size_t)a.r[q] * D;
     const long long c0 = a.qptr[q];
     const int n = (int)(a.qptr[q + 1] - c0);
     const int nv = n + 1;
-    const int* crel = a.crel + c0;
-    const int* ccol = a.ccol + c0;
-    const int* crole = a.crole + c0;
     const int* cpartner = a.cpartner + c0;
     const int* celig = a.celig + c0;
-    const int* cstep = a.cstep + c0;
-    const float* cval = a.cval + c0;
-    const int k = tid % D, grp = tid / D;
+    CfKeep keep;
+    keep.cstep = a.cstep + c0;
+    keep.later = step > 0;
     bool staged = false;
 
     for (int v0 = (blockIdx.x % tiles) * CV_VT; v0 < nv; v0 += tiles * CV_VT) {
-        // variants past the last repeat it (computed, never stored); jv: the candidate a variant drops, -1: none
-        int jv[CV_VT], pv[CV_VT];
+        // variants past the last repeat it (computed, never stored)
         bool store[CV_VT];
         bool any = false;
 #pragma unroll
         for (int u = 0; u < CV_VT; ++u) {
             const int vi = v0 + u < nv ? v0 + u : nv - 1;
-            jv[u] = vi - 1;
-            pv[u] = -1;
+            keep.jv[u] = vi - 1;
+            keep.pv[u] = -1;
             store[u] = false;
             if (v0 + u < nv) {
                 if (vi == 0) {
                     store[u] = step == 0;
                 } else {
-                    pv[u] = cpartner[vi - 1];
-                    store[u] = celig[vi - 1] != 0 && (step == 0 || cstep[vi - 1] < 0);
+                    keep.pv[u] = cpartner[vi - 1];
+                    store[u] = celig[vi - 1] != 0 && (step == 0 || keep.cstep[vi - 1] < 0);
                 }
             }
             any = any || store[u];
         }
         if (!any) continue;                    // uniform over the workgroup
 
-        if (!staged) {
-            // the relation segments of the candidate list and the staged E rows
-            if (tid <= MAX_R) rstart[tid] = n;
-            __syncthreads();
-            for (int j = tid; j < n; j += NT) {
-                const int r1 = crel[j];
-                const int r0 = j ? crel[j - 1] : -1;
-                for (int r = r0 + 1; r <= r1; ++r) rstart[r] = j;
-            }
-            const int ns = n < ES_ROWS ? n : ES_ROWS;
-            for (int idx = tid; idx < ns * D; idx += NT) es[idx] = a.E[(size_t)ccol[idx / D] * D + idx % D];
-            staged = true;
-        }
-        // x^0 = E[h] / E[t] in every variant (the last tile's readers of x are past a barrier)
-        for (int idx = tid; idx < CV_ROWS * D; idx += NT) {
-            const int row = idx / D;
-            x[0][row][idx % D] = a.E[(size_t)((row & 1) ? tt : hh) * D + idx % D];
-        }
-        __syncthreads();
-
-        // AE rows of every variant: curves_kernel's chains, a dropped candidate enters with a zero multiplier
-#pragma unroll
-        for (int ri = 0; ri < RPG; ++ri) {
-            const int r = grp + ri * GR;
-            if (r < R) {
-                float acc[CV_ROWS];
-#pragma unroll
-                for (int j = 0; j < CV_ROWS; ++j) acc[j] = 0.f;
-                const int j1 = rstart[r + 1];
-                for (int j = rstart[r]; j < j1; ++j) {
-                    const float val = cval[j];
-                    const int role = crole[j];
-                    const bool gone = step > 0 && cstep[j] >= 0;
-                    const float ev = j < ES_ROWS ? es[j * D + k] : a.E[(size_t)ccol[j] * D + k];
-                    const float vh = (role & 1) ? val : 0.f, vt = (role & 2) ? val : 0.f;
-#pragma unroll
-                    for (int u = 0; u < CV_VT; ++u) {
-                        const bool keep = !gone && j != jv[u] && j != pv[u];
-                        acc[2 * u] = fmaf(keep ? vh : 0.f, ev, acc[2 * u]);
-                        acc[2 * u + 1] = fmaf(keep ? vt : 0.f, ev, acc[2 * u + 1]);
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < CV_ROWS; ++j) AE[r][j][k] = acc[j];
-            }
-        }
-        __syncthreads();
-
-        // forward: the reference layer on the CV_ROWS rows, as in curves_kernel
-        for (int l = 0; l < 3; ++l) {
-            const int cur = l & 1;
-            for (int item = grp; item < CV_VT * R; item += GR) {
-                const int u = item / R, r = item % R;
-                const float z = group_sum<D>(x[cur][2 * u][k] * a.Wa[l][(size_t)k * R + r]);
-                if (k == 0) zs[u][r] = z + a.ba[l][r];
-            }
-#pragma unroll
-            for (int ri = 0; ri < RPG; ++ri) {
-                const int r = grp + ri * GR;
-                if (r < R) {
-                    float y[CV_ROWS];
-                    matvec_rows<D, CV_ROWS>(a.K[l] + (size_t)r * D * D + k, &AE[r][0][0], D, y);
-#pragma unroll
-                    for (int j = 0; j < CV_ROWS; ++j) P[r][j][k] = y[j];
-                }
-            }
-            __syncthreads();
-            if (tid < CV_VT * R) {
-                const int u = tid / R, r = tid % R;
-                float mx = -INFINITY;
-                for (int i = 0; i < R; ++i) mx = fmaxf(mx, zs[u][i]);
-                float sum = 0.f;
-                for (int i = 0; i < R; ++i) sum += expf(zs[u][i] - mx);
-                w[u][r] = sigmoid_ref(expf(zs[u][r] - mx) / sum);
-            }
-            __syncthreads();
-            {
-                float y[RW];
-                matvec_rows<D, RW>(a.S[l] + k, &x[cur][grp * RW][0], D, y);
-#pragma unroll
-                for (int j = 0; j < RW; ++j) {
-                    const int row = grp * RW + j;
-                    float v = y[j];
-                    for (int r = 0; r < R; ++r) v = fmaf(w[row >> 1][r], P[r][row][k], v);
-                    x[1 - cur][row][k] = sigmoid_ref(v);
-                }
-            }
-            __syncthreads();
-        }
-
-        // DistMult of every variant (x^3 sits in x[1])
-        for (int u = grp; u < CV_VT; u += GR) {
-            const float s = group_sum<D>(x[1][2 * u][k] * a.rel[(size_t)rr * D + k] * x[1][2 * u + 1][k]);
-            if (k == 0 && store[u]) {
-                if (jv[u] < 0)
-                    a.path[(size_t)q * (a.k + 1)] = sigmoid_ref(s);
+        tile_begin<D>(T, a, c0, n, hh, tt, !staged);       // the last tile's readers of x are past a barrier
+        staged = true;
+        tile_ae<D>(T, a, c0, keep);
+        tile_forward<D>(T, a);
+        for (int u = threadIdx.x / D; u < CV_VT; u += Tile<D>::GR) {
+            const float p = tile_score<D>(T, rl, u);
+            // a stored variant is v0 + u itself: the base, or the one that drops candidate v0 + u - 1.  (The keep table
+            // is indexed by constants only, so it stays in registers.)
+            if (threadIdx.x % D == 0 && store[u]) {
+                if (v0 + u == 0)
+                    a.path[(size_t)q * (a.k + 1)] = p;
                 else
-                    vals[c0 + jv[u]] = sigmoid_ref(s);
+                    vals[c0 + v0 + u - 1] = p;
             }
         }
         __syncthreads();                       // x[1] is read above, x[0] rewritten by the next tile
@@ -1238,13 +1210,7 @@ __global__ __launch_bounds__(NT) void ig_path_kernel(const PathP pp) {
     const int side2 = (tid / D) & 1;
 
     // the relation segments of the candidate list, x^0, the staged matrices
-    if (tid <= MAX_R) rstart[tid] = n;
-    __syncthreads();
-    for (int j = tid; j < n; j += NT) {
-        const int r1 = crel[j];
-        const int r0 = j ? crel[j - 1] : -1;
-        for (int r = r0 + 1; r <= r1; ++r) rstart[r] = j;
-    }
+    rstart_scan(rstart, crel, n);
     if (tid < 2 * D) x[0][side2][k] = a.E[(size_t)(side2 ? tt : hh) * D + k];
     if (tid < D) rels[k] = a.rel[(size_t)rr * D + k];
     for (int idx = tid; idx < D * D; idx += NT) {
@@ -1309,11 +1275,7 @@ __global__ __launch_bounds__(NT) void ig_path_kernel(const PathP pp) {
     if (tid < 2 * D) c1[side2][k] = matvec1<D>(a.S[0] + k, x[0][side2]);
     __syncthreads();
     if (tid < R) {
-        float mx = -INFINITY;
-        for (int i = 0; i < R; ++i) mx = fmaxf(mx, zs[i]);
-        float sum = 0.f;
-        for (int i = 0; i < R; ++i) sum += expf(zs[i] - mx);
-        const float s = expf(zs[tid] - mx) / sum;
+        const float s = rel_softmax(zs, R, tid);
         sm[0][tid] = s;
         w[0][tid] = sigmoid_ref(s);
     }
@@ -1344,11 +1306,7 @@ __global__ __launch_bounds__(NT) void ig_path_kernel(const PathP pp) {
             }
             __syncthreads();
             if (tid < R) {
-                float mx = -INFINITY;
-                for (int i = 0; i < R; ++i) mx = fmaxf(mx, zs[i]);
-                float sum = 0.f;
-                for (int i = 0; i < R; ++i) sum += expf(zs[i] - mx);
-                const float s = expf(zs[tid] - mx) / sum;
+                const float s = rel_softmax(zs, R, tid);
                 sm[l][tid] = s;
                 w[l][tid] = sigmoid_ref(s);
             }
@@ -1392,19 +1350,11 @@ __global__ __launch_bounds__(NT) void ig_path_kernel(const PathP pp) {
                 if (k == 0) da[r] = dw * (wv * (1.0f - wv));
             }
             __syncthreads();
-            if (tid < R) {
-                float sum = 0.f;
-                for (int i = 0; i < R; ++i) sum = fmaf(sm[l][i], da[i], sum);
-                du[tid] = sm[l][tid] * (da[tid] - sum);
-            }
+            if (tid < R) du[tid] = rel_softmax_bwd(sm[l], da, R, tid);
             __syncthreads();
-            // dx^{l-1} = dz S^l^T (+ du Walpha^l^T on the head side)
-            if (tid < 2 * D) {
-                float v = matvec1<D>(&STm[l - 1][k], dz[side2]);
-                if (side2 == 0)
-                    for (int r = 0; r < R; ++r) v = fmaf(du[r], Was[l - 1][k * R + r], v);
-                dx[side2][k] = v;
-            }
+            // dx^{l-1} = dz S^l^T (+ du Walpha^l^T on the head side), from the LDS copies
+            if (tid < 2 * D)
+                dx[side2][k] = dx_step<D>(&STm[l - 1][k], dz[side2], side2 == 0, du, &Was[l - 1][k * R], R);
             __syncthreads();
         }
     }

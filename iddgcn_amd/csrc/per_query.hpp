@@ -40,8 +40,10 @@ __device__ __forceinline__ void st4(float* p, f32x4 v) { *(f32x4*)p = v; }
 
 // selection (rank_topk_kernel, topk_kernel): passes of TK_CH candidates merged into the running top 64.  The merge pass
 // itself (key store, bitonic sort, running-top update) is written out in both kernels: as a function here it compiled
-// to other scalar register numbers and another order of constant moves.  So did the relation-segment scan (rstart)
-// and the E-row staging (es) that mask_explain_kernel and curves_kernel share: both stay written out in explain.hip.
+// to other scalar register numbers and another order of constant moves, and the rule for these kernels is an
+// identical digest.  The relation-segment scan (rstart) and the E-row staging (es) of the fused explainer kernels
+// stayed written out for the same reason until those kernels' rule became bitwise results within the same budget
+// (profiles/r21/): they are functions of explain.hip now.
 constexpr int TK_BUF = 1024;                           // keys sorted per pass
 constexpr int TK_CH = TK_BUF - IDDGCN_TOPK_MAX;        // new candidates per pass; buf[TK_CH..) holds the running top
 
